@@ -9,7 +9,9 @@ torch.distributed.run) the per-GPU work is held fixed (weak scaling) on BASELINE
 O1280 at N=8 (configs 4 and 5; O1280 / 8 is 2x the per-GPU points of O320), sharded into contiguous sea-point ranges with a
 point-to-point halo exchange over RCCL.
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times --steps steps in one window and prints the headline figures;
+--full adds what takes extra time or runs of its own: the median of --repeats windows, per-kernel times, the roofline object, the
+swh norms and the CPU baseline.  --dump-outputs DIR writes what the last timed step handed its caller (dump_outputs).
 """
 from __future__ import annotations
 
@@ -141,14 +143,36 @@ def cpu_baseline(nang: int, nfre: int, prec: str, target_s: float = 9.0, ng: int
     return out
 
 
+DUMP_BYTES = 48e6      # --dump-outputs: the sample of sea points is sized to this many bytes (the spectra alone are 2.2 GB at O320 sp)
+
+
+def dump_outputs(m, path: str) -> None:
+    """The arrays one WAMINTGR step hands its caller, after the last timed step: FL1 (spectra), XLLWS (wind-sea mask), FF (forcing with
+    the friction velocity and roughness IMPLSCH updates), INTF (fluxes and coupling outputs) and MIJ (last prognostic frequency, as
+    float32), each at the same seeded sample of sea points (every point when they fit DUMP_BYTES), as <path>/<name>.npy."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {"fl1": m.fl1, "xllws": m.xllws, "ff": m.ff, "intf": m.intf, "mij": m.mij}
+    per_point = sum(t[0].numel() * t.element_size() for t in arrays.values())
+    k = min(m.n, int(DUMP_BYTES // per_point))
+    idx = np.arange(m.n) if k == m.n else np.sort(np.random.default_rng(0).choice(m.n, k, replace=False))
+    ix = torch.from_numpy(idx).to(m.dev)
+    for name, t in arrays.items():
+        a = t[ix].cpu().numpy()
+        np.save(os.path.join(path, f"{name}.npy"), a if a.dtype in (np.float32, np.float64) else a.astype(np.float32))
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--repeats", type=int, default=5,
-                    help="timed windows of --steps steps each, every one bracketed by barrier + synchronize; the MEDIAN window is reported "
-                         "(SURVEY.md 8d: median of 5), min / max next to it")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: --repeats windows (median reported), per-kernel times, roofline, swh norms, CPU baseline")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write FL1 / XLLWS / FF / INTF / MIJ of the last step at a seeded sample of sea points to DIR/<name>.npy")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="--full: timed windows of --steps steps each, every one bracketed by barrier + synchronize; the MEDIAN window is "
+                         "reported (SURVEY.md 8d: median of 5, the default), min / max next to it.  A plain run times one window")
     ap.add_argument("--grid", type=int, default=0, help="octahedral resolution (default 320*sqrt(gpus))")
     ap.add_argument("--prec", default="sp", choices=["sp", "dp"])
     ap.add_argument("--nang", type=int, default=36)
@@ -193,8 +217,14 @@ def main() -> None:
                     help="refraction: 0 none (BASELINE configurations), 1 depth, 2 currents, 3 both (synthetic current field)")
     a = ap.parse_args()
 
+    if a.repeats is None:
+        a.repeats = 5 if a.full else 1
     if a.gpus < 1 or a.steps < 1 or a.repeats < 1:
         raise SystemExit("--gpus, --steps and --repeats must be >= 1")
+    if not a.full and (a.repeats != 1 or a.pmc_file):
+        raise SystemExit("bench.py: --repeats > 1 and --pmc-file need --full (a plain run times --steps steps once)")
+    if a.dump_outputs and a.gpus > 1:
+        raise SystemExit("bench.py: --dump-outputs writes one rank's outputs: use it with --gpus 1")
     if a.strict_halo is None:
         a.strict_halo = not a.share_gpu
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -344,12 +374,17 @@ def main() -> None:
     for _ in range(a.warmup):
         step_untimed()
     # a.repeats windows of a.steps steps, each bracketed by barrier + synchronize on both sides; a window's time is the MAX over ranks,
-    # the reported one the median window.  Kernel times: HIP events on the launch stream around PROPAG_WAM and IMPLSCH of every step.
-    m.halo_events = [] if world > 1 else None      # N > 1: the compute stream's wait at the end of every exchange (Wamintgr.propag)
+    # the reported one the median window.  Kernel times (--full): HIP events on the launch stream around PROPAG_WAM and IMPLSCH of every step.
+    m.halo_events = [] if world > 1 and a.full else None      # N > 1: the compute stream's wait at the end of every exchange (Wamintgr.propag)
     windows, kt = [], []
+
+    class NoEvent:      # a plain run records no kernel events
+        def record(self):
+            pass
+
     for _ in range(a.repeats):
         sync()
-        ev = [[torch.cuda.Event(enable_timing=True) for _ in range(4)] for _ in range(a.steps)]
+        ev = [[torch.cuda.Event(enable_timing=True) if a.full else NoEvent() for _ in range(4)] for _ in range(a.steps)]
         if m.halo_events is not None:
             m.halo_events.clear()
         t0 = time.perf_counter()
@@ -378,8 +413,9 @@ def main() -> None:
                 host_fl.copy_(m.fl1[: m.n], non_blocking=True)
         sync()
         windows.append(time.perf_counter() - t0)
-        hw = sum(x.elapsed_time(y) for x, y in m.halo_events) / a.steps if m.halo_events else 0.0
-        kt.append((sum(e[0].elapsed_time(e[1]) for e in ev) / a.steps, sum(e[2].elapsed_time(e[3]) for e in ev) / a.steps, hw))
+        if a.full:
+            hw = sum(x.elapsed_time(y) for x, y in m.halo_events) / a.steps if m.halo_events else 0.0
+            kt.append((sum(e[0].elapsed_time(e[1]) for e in ev) / a.steps, sum(e[2].elapsed_time(e[3]) for e in ev) / a.steps, hw))
     m.halo_events = None
     per_rank = None
     if dist is not None:
@@ -390,57 +426,24 @@ def main() -> None:
     order_w = sorted(range(a.repeats), key=lambda i: windows[i])
     imed = order_w[(a.repeats - 1) // 2]        # the median window (the lower one of an even count)
     el = windows[imed]
-    t_prop, t_impl, t_wait = kt[imed]
-    if dist is not None:
-        mine = torch.tensor([t_prop, t_impl, t_wait], dtype=torch.float64, device=dev)
-        allr = [torch.zeros_like(mine) for _ in range(world)]
-        dist.all_gather(allr, mine)
-        per_rank = [[float(v) for v in x.cpu()] for x in allr]
-        t_prop, t_impl = max(r_[0] for r_ in per_rank), max(r_[1] for r_ in per_rank)
+    if a.full:
+        t_prop, t_impl, t_wait = kt[imed]
+        if dist is not None:
+            mine = torch.tensor([t_prop, t_impl, t_wait], dtype=torch.float64, device=dev)
+            allr = [torch.zeros_like(mine) for _ in range(world)]
+            dist.all_gather(allr, mine)
+            per_rank = [[float(v) for v in x.cpu()] for x in allr]
+            t_prop, t_impl = max(r_[0] for r_ in per_rank), max(r_[1] for r_ in per_rank)
     if a.dump:
         np.save(f"{a.dump}.{rank}.npy", m.fl1[: m.n].cpu().numpy())
-    swh = m.swh()
-    finite = bool(torch.isfinite(swh).all().item())
-    swh_avg, swh_min, swh_max, _ = m.swh_norm()      # OUTWNORM of the significant wave height, computed on the device
+    if a.dump_outputs:
+        dump_outputs(m, a.dump_outputs)
+    if a.full:
+        swh = m.swh()
+        finite = bool(torch.isfinite(swh).all().item())
+        swh_avg, swh_min, swh_max, _ = m.swh_norm()      # OUTWNORM of the significant wave height, computed on the device
 
     if rank == 0:
-        w = 4 if a.prec == "sp" else 8
-        N, NR = a.nang * a.nfre, a.nang * cfg.nfre_red
-        b_impl = w * (3 * N + 5 * a.nfre + 55)          # F r+w, XLLWS w, 5 per-frequency props, ~55 scalars
-        if a.irefra:
-            b_prop = w * (2 * NR + 3 * a.nfre + 2 * a.nang + 18) + 60   # + own OMOSNH2KD / WAVNUM rows and the REFR row
-        elif a.weights == "stored":
-            b_prop = w * 10 * NR + 56                    # 8 weights + F1 + F3, 14 int32 neighbour ids
-        else:
-            b_prop = w * (2 * NR + a.nfre + 13) + 60     # F1 + F3 + own CGROUP row + point geometry, 15 int32 ids
-        # vector flops per point-step (IMPLSCH 0.47 Mflop at 36 x 36; the advection: 61 per spectral bin = 8 multiply-adds of the
-        # stencil + the rebuild of the eight weights in their hoisted form, csrc/ctu.h) against the 157.3 TFLOP/s fp32 vector peak (78.6 fp64)
-        fl_impl = 0.47e6 * (a.nang * a.nfre) / 1296.0
-        fl_prop = 61.0 * NR
-        if fused:
-            # ONE kernel per step: F1 read, F3 written, XLLWS written, the five per-frequency properties, the own CGROUP row and point geometry
-            # of the weights, ~68 scalars, 15 int32 neighbour ids -- the advected spectrum never goes to memory (2 N w bytes less than the
-            # two kernels together)
-            b_step = w * (3 * N + 6 * a.nfre + 68) + 60
-            kern = {"implsch_adv": {"ms": t_impl, "alg_bytes": b_step * m.n, "gbs": b_step * m.n / t_impl / 1e6, "flop": (fl_impl + fl_prop) * m.n,
-                                    "what": "k_implsch4<..., ADV = 1 | 3>: PROPAGS2 inside IMPLSCH's tile load (+ k_ctu_prep, k_implsch4_pre / _fin"
-                                            + (", + the fast waves' sub-steps on compact rows" if a.ifrelfmax else "") + ")"}}
-            if a.adv_per_source > 1:      # the advection steps before the last one: PROPAGS2 on its own
-                kern["propags2"] = {"ms": t_prop, "alg_bytes": b_prop * m.n * (a.adv_per_source - 1),
-                                    "gbs": b_prop * m.n * (a.adv_per_source - 1) / t_prop / 1e6, "flop": fl_prop * m.n * (a.adv_per_source - 1)}
-        else:
-            kern = {
-                "propags2": {"ms": t_prop, "alg_bytes": b_prop * m.n * a.adv_per_source,
-                             "gbs": b_prop * m.n * a.adv_per_source / t_prop / 1e6, "flop": fl_prop * m.n * a.adv_per_source},
-                "implsch": {"ms": t_impl, "alg_bytes": b_impl * m.n, "gbs": b_impl * m.n / t_impl / 1e6, "flop": fl_impl * m.n},
-            }
-        dom = max(kern, key=lambda k: kern[k]["ms"])
-        # HBM traffic and the busy fractions of the vector ALU and the LDS are NOT measured in this run: they come from a counter summary
-        # tools/pmc_bench.py took with rocprofv3 --pmc on this very command (profiles/r05_bench_O320_sp_pmc.json: separate passes for the SQ
-        # sets, FETCH_SIZE and WRITE_SIZE; FETCH_SIZE doubled as MI355X_MICROARCH.md prescribes for gfx950, calibrated on a copy in
-        # profiles/r02_fetch_size_calibration.json).  The summary is attached only when it describes THIS workload and THIS kernel: its workload
-        # string and dtype must equal the run's and its kernel must be the instantiation the run launches; a file given with --pmc-file that
-        # does not match is refused.
         workload = (f"O{ng} all-ocean octahedral grid, {grid.nsea} sea points, {a.nang} dir x {a.nfre} freq "
                     f"(NFRE_RED={cfg.nfre_red}), full WAMINTGR step = PROPAGS2 advection + NEWWIND + IMPLSCH"
                     + (" as one kernel (PROPAGS2 inside IMPLSCH's tile load)" if fused else "") + ", "
@@ -451,61 +454,97 @@ def main() -> None:
                     + (f", fast waves M<={a.ifrelfmax} in two sub-steps" if a.ifrelfmax else "")
                     + (", DIAGNOSTIC: spectra copied from and to pinned host memory every step" if a.host_state else ""))
         dtype = "f32" if a.prec == "sp" else "f64"
-        here = os.path.dirname(os.path.abspath(__file__))
-        pmc_path = a.pmc_file or os.path.join(here, "profiles", f"r06_bench_O{ng}_{a.prec}_pmc.json")
-        pmc, pmc_why = None, None
-        from ecwam_amd import lib as L
-        lib_file = L.LIBPATH      # (ECWAM_HIP_LIB, or the product library)
-        lib_sha = hashlib.sha256(open(lib_file, "rb").read()).hexdigest()
-        if os.path.exists(pmc_path) and world == 1:
-            with open(pmc_path) as fh:
-                cand = json.load(fh)
-            ck = "implsch" if dom.startswith("implsch") else dom
-            kname = (cand.get("kernels", {}).get(ck, {}) or {}).get("name") or ""
-            tn = "float" if a.prec == "sp" else "double"
-            want_k = {"implsch": f"k_implsch4<{tn}, {a.nang}, ", "propags2": "k_propags2"}[ck]
-            adv_ok = (kname.rstrip(">").split(",")[-1].strip() == ("1" if fused else "0")) if ck == "implsch" else True
-            if cand.get("workload", {}).get("workload") != workload or cand.get("workload", {}).get("dtype") != dtype:
-                pmc_why = "the summary was taken on another workload: " + str(cand.get("workload", {}).get("workload"))
-            elif want_k not in kname or not adv_ok:
-                pmc_why = f"the summary's kernel is {kname!r}, this run launches {want_k}...>" + (" with the advecting tile load" if fused else "")
-            elif cand.get("library", {}).get("sha256") != lib_sha:
-                pmc_why = (f"the summary was taken on another build of the library (sha256 {str(cand.get('library', {}).get('sha256'))[:16]}..., "
-                           f"this run loaded {lib_sha[:16]}...)")
+        if a.full:
+            w = 4 if a.prec == "sp" else 8
+            N, NR = a.nang * a.nfre, a.nang * cfg.nfre_red
+            b_impl = w * (3 * N + 5 * a.nfre + 55)          # F r+w, XLLWS w, 5 per-frequency props, ~55 scalars
+            if a.irefra:
+                b_prop = w * (2 * NR + 3 * a.nfre + 2 * a.nang + 18) + 60   # + own OMOSNH2KD / WAVNUM rows and the REFR row
+            elif a.weights == "stored":
+                b_prop = w * 10 * NR + 56                    # 8 weights + F1 + F3, 14 int32 neighbour ids
             else:
-                pmc = cand["kernels"][ck]
-        elif a.pmc_file:
-            pmc_why = "no such file" if not os.path.exists(pmc_path) else "counter summaries describe one GPU"
-        elif world == 1:
-            pmc_why = "no counter summary for this workload under profiles/"
-        if a.pmc_file and pmc is None:
-            raise SystemExit(f"bench.py: --pmc-file {a.pmc_file} refused: {pmc_why}")
-        vec_peak = VALU_PEAK_TFLOPS[a.prec]
-        roof = {"bound": "hbm", "kernel": dom, "achieved": kern[dom]["gbs"], "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": kern[dom]["gbs"] / HBM_PEAK_GBS,
-                "traffic": None,
-                # the roof that binds this kernel (above the fp32 ridge): its vector flops against the vector peak
-                "valu_frac": kern[dom]["flop"] / (kern[dom]["ms"] * 1e-3) / (vec_peak * 1e12), "valu_peak_tflops": vec_peak,
-                "valu_busy": None, "lds_busy": None, "counters": None, "counters_why_null": pmc_why, "library_sha256": lib_sha}
-        if pmc is not None:
-            # one story: the fraction of the HBM roofline on algorithmic bytes (the contract's figure), the bytes the kernel really moved,
-            # and what its own counters say limits it -- the busy fractions of a SIMD's vector ALU and of the CU's LDS array at the resident
-            # wave count (IMPLSCH: two waves per SIMD in single precision).  `bound` follows the counters: "hbm" only for a kernel that moves
-            # its bytes at more than half the peak, else the busiest unit
-            vb, lb = pmc.get("valu_busy"), pmc.get("lds_busy")
-            hbm_frac_real = (pmc.get("hbm_bytes") or 0.0) / (kern[dom]["ms"] * 1e-3) / (HBM_PEAK_GBS * 1e9)
-            bound = "hbm" if hbm_frac_real > 0.5 else ("valu+lds" if (vb or 0) > 0.5 and (lb or 0) > 0.4 else ("valu" if (vb or 0) > 0.5 else "latency"))
-            roof.update({"bound": bound, "traffic": pmc.get("hbm_bytes"), "valu_busy": vb, "lds_busy": lb, "hbm_frac_of_moved_bytes": hbm_frac_real,
-                         "limiter": "vector ALU + LDS at the resident wave count, not HBM" if dom.startswith("implsch") else "gather latency / instruction issue",
-                         "counters": {"file": os.path.relpath(pmc_path, here), "kernel": pmc.get("name"), "library_sha256": lib_sha,
-                                      "not_measured_live": True, "valu_insts_per_point": pmc.get("per_point", {}).get("SQ_INSTS_VALU"),
-                                      "waitcnt_fraction": pmc.get("waitcnt_fraction"), "lds_bank_conflict_share": pmc.get("lds_bank_conflict_share")}})
-            roof.pop("counters_why_null")
+                b_prop = w * (2 * NR + a.nfre + 13) + 60     # F1 + F3 + own CGROUP row + point geometry, 15 int32 ids
+            # vector flops per point-step (IMPLSCH 0.47 Mflop at 36 x 36; the advection: 61 per spectral bin = 8 multiply-adds of the
+            # stencil + the rebuild of the eight weights in their hoisted form, csrc/ctu.h) against the 157.3 TFLOP/s fp32 vector peak (78.6 fp64)
+            fl_impl = 0.47e6 * (a.nang * a.nfre) / 1296.0
+            fl_prop = 61.0 * NR
+            if fused:
+                # ONE kernel per step: F1 read, F3 written, XLLWS written, the five per-frequency properties, the own CGROUP row and point geometry
+                # of the weights, ~68 scalars, 15 int32 neighbour ids -- the advected spectrum never goes to memory (2 N w bytes less than the
+                # two kernels together)
+                b_step = w * (3 * N + 6 * a.nfre + 68) + 60
+                kern = {"implsch_adv": {"ms": t_impl, "alg_bytes": b_step * m.n, "gbs": b_step * m.n / t_impl / 1e6, "flop": (fl_impl + fl_prop) * m.n,
+                                        "what": "k_implsch4<..., ADV = 1 | 3>: PROPAGS2 inside IMPLSCH's tile load (+ k_ctu_prep, k_implsch4_pre / _fin"
+                                                + (", + the fast waves' sub-steps on compact rows" if a.ifrelfmax else "") + ")"}}
+                if a.adv_per_source > 1:      # the advection steps before the last one: PROPAGS2 on its own
+                    kern["propags2"] = {"ms": t_prop, "alg_bytes": b_prop * m.n * (a.adv_per_source - 1),
+                                        "gbs": b_prop * m.n * (a.adv_per_source - 1) / t_prop / 1e6, "flop": fl_prop * m.n * (a.adv_per_source - 1)}
+            else:
+                kern = {
+                    "propags2": {"ms": t_prop, "alg_bytes": b_prop * m.n * a.adv_per_source,
+                                 "gbs": b_prop * m.n * a.adv_per_source / t_prop / 1e6, "flop": fl_prop * m.n * a.adv_per_source},
+                    "implsch": {"ms": t_impl, "alg_bytes": b_impl * m.n, "gbs": b_impl * m.n / t_impl / 1e6, "flop": fl_impl * m.n},
+                }
+            dom = max(kern, key=lambda k: kern[k]["ms"])
+            # HBM traffic and the busy fractions of the vector ALU and the LDS are NOT measured in this run: they come from a counter summary
+            # tools/pmc_bench.py took with rocprofv3 --pmc on this very command (profiles/r05_bench_O320_sp_pmc.json: separate passes for the SQ
+            # sets, FETCH_SIZE and WRITE_SIZE; FETCH_SIZE doubled as MI355X_MICROARCH.md prescribes for gfx950, calibrated on a copy in
+            # profiles/r02_fetch_size_calibration.json).  The summary is attached only when it describes THIS workload and THIS kernel: its workload
+            # string and dtype must equal the run's and its kernel must be the instantiation the run launches; a file given with --pmc-file that
+            # does not match is refused.
+            here = os.path.dirname(os.path.abspath(__file__))
+            pmc_path = a.pmc_file or os.path.join(here, "profiles", f"r06_bench_O{ng}_{a.prec}_pmc.json")
+            pmc, pmc_why = None, None
+            from ecwam_amd import lib as L
+            lib_file = L.LIBPATH      # (ECWAM_HIP_LIB, or the product library)
+            lib_sha = hashlib.sha256(open(lib_file, "rb").read()).hexdigest()
+            if os.path.exists(pmc_path) and world == 1:
+                with open(pmc_path) as fh:
+                    cand = json.load(fh)
+                ck = "implsch" if dom.startswith("implsch") else dom
+                kname = (cand.get("kernels", {}).get(ck, {}) or {}).get("name") or ""
+                tn = "float" if a.prec == "sp" else "double"
+                want_k = {"implsch": f"k_implsch4<{tn}, {a.nang}, ", "propags2": "k_propags2"}[ck]
+                adv_ok = (kname.rstrip(">").split(",")[-1].strip() == ("1" if fused else "0")) if ck == "implsch" else True
+                if cand.get("workload", {}).get("workload") != workload or cand.get("workload", {}).get("dtype") != dtype:
+                    pmc_why = "the summary was taken on another workload: " + str(cand.get("workload", {}).get("workload"))
+                elif want_k not in kname or not adv_ok:
+                    pmc_why = f"the summary's kernel is {kname!r}, this run launches {want_k}...>" + (" with the advecting tile load" if fused else "")
+                elif cand.get("library", {}).get("sha256") != lib_sha:
+                    pmc_why = (f"the summary was taken on another build of the library (sha256 {str(cand.get('library', {}).get('sha256'))[:16]}..., "
+                               f"this run loaded {lib_sha[:16]}...)")
+                else:
+                    pmc = cand["kernels"][ck]
+            elif a.pmc_file:
+                pmc_why = "no such file" if not os.path.exists(pmc_path) else "counter summaries describe one GPU"
+            elif world == 1:
+                pmc_why = "no counter summary for this workload under profiles/"
+            if a.pmc_file and pmc is None:
+                raise SystemExit(f"bench.py: --pmc-file {a.pmc_file} refused: {pmc_why}")
+            vec_peak = VALU_PEAK_TFLOPS[a.prec]
+            roof = {"bound": "hbm", "kernel": dom, "achieved": kern[dom]["gbs"], "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": kern[dom]["gbs"] / HBM_PEAK_GBS,
+                    "traffic": None,
+                    # the roof that binds this kernel (above the fp32 ridge): its vector flops against the vector peak
+                    "valu_frac": kern[dom]["flop"] / (kern[dom]["ms"] * 1e-3) / (vec_peak * 1e12), "valu_peak_tflops": vec_peak,
+                    "valu_busy": None, "lds_busy": None, "counters": None, "counters_why_null": pmc_why, "library_sha256": lib_sha}
+            if pmc is not None:
+                # one story: the fraction of the HBM roofline on algorithmic bytes (the contract's figure), the bytes the kernel really moved,
+                # and what its own counters say limits it -- the busy fractions of a SIMD's vector ALU and of the CU's LDS array at the resident
+                # wave count (IMPLSCH: two waves per SIMD in single precision).  `bound` follows the counters: "hbm" only for a kernel that moves
+                # its bytes at more than half the peak, else the busiest unit
+                vb, lb = pmc.get("valu_busy"), pmc.get("lds_busy")
+                hbm_frac_real = (pmc.get("hbm_bytes") or 0.0) / (kern[dom]["ms"] * 1e-3) / (HBM_PEAK_GBS * 1e9)
+                bound = "hbm" if hbm_frac_real > 0.5 else ("valu+lds" if (vb or 0) > 0.5 and (lb or 0) > 0.4 else ("valu" if (vb or 0) > 0.5 else "latency"))
+                roof.update({"bound": bound, "traffic": pmc.get("hbm_bytes"), "valu_busy": vb, "lds_busy": lb, "hbm_frac_of_moved_bytes": hbm_frac_real,
+                             "limiter": "vector ALU + LDS at the resident wave count, not HBM" if dom.startswith("implsch") else "gather latency / instruction issue",
+                             "counters": {"file": os.path.relpath(pmc_path, here), "kernel": pmc.get("name"), "library_sha256": lib_sha,
+                                          "not_measured_live": True, "valu_insts_per_point": pmc.get("per_point", {}).get("SQ_INSTS_VALU"),
+                                          "waitcnt_fraction": pmc.get("waitcnt_fraction"), "lds_bank_conflict_share": pmc.get("lds_bank_conflict_share")}})
+                roof.pop("counters_why_null")
         out = {
             "metric": f"grid-point spectral steps/sec (whole node) at O{ng}, {a.nang}dir x {a.nfre}freq",
             "value": grid.nsea * a.steps / el, "unit": "grid-point spectral steps/s", "n_gpus": world, "steps": a.steps,
             "warmup": a.warmup, "ms_per_step": el / a.steps * 1e3, "higher_is_better": True, "scaling": "weak",
-            "repeats": a.repeats, "window_ms": {"median": el * 1e3, "min": min(windows) * 1e3, "max": max(windows) * 1e3,
-                                                "all": [w_ * 1e3 for w_ in windows]},
             "vs_baseline": None, "dtype": dtype, "data": "synthetic",
             "config": {"workload": workload,
                        "points_per_gpu": m.n, "halo_points": m.dom.nh, "parallelism": f"sea-point block x{world}",
@@ -518,17 +557,22 @@ def main() -> None:
                                          "near the poles of the all-ocean grid (ctuw.F90:637), 450 s passes; scaled with the grid spacing "
                                          "beyond O320.  The work per step does not depend on the time step",
                        "ranks": world, "share_gpu": bool(a.share_gpu)},
-            # N > 1, per rank [PROPAG_WAM ms, IMPLSCH ms, of PROPAG_WAM: the compute stream waiting for the halo exchange at halo_finish]:
-            # the exchange is posted first and the rows that read no halo row (decomp.interior) are advected while it runs, so the wait
-            # is what the overlap did not hide
-            "propag_split_per_rank": ([{"rank": i, "propag_ms": r_[0], "implsch_ms": r_[1], "halo_wait_ms": r_[2], "stencil_ms": r_[0] - r_[2]}
-                                       for i, r_ in enumerate(per_rank)] if per_rank else None),
-            "roofline": roof,
-            "kernels": kern,
-            "finite": finite,
-            "swh_norm_rank0": {"avg": swh_avg, "min": swh_min, "max": swh_max},
         }
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full:
+            out.update({
+                "repeats": a.repeats, "window_ms": {"median": el * 1e3, "min": min(windows) * 1e3, "max": max(windows) * 1e3,
+                                                    "all": [w_ * 1e3 for w_ in windows]},
+                # N > 1, per rank [PROPAG_WAM ms, IMPLSCH ms, of PROPAG_WAM: the compute stream waiting for the halo exchange at halo_finish]:
+                # the exchange is posted first and the rows that read no halo row (decomp.interior) are advected while it runs, so the wait
+                # is what the overlap did not hide
+                "propag_split_per_rank": ([{"rank": i, "propag_ms": r_[0], "implsch_ms": r_[1], "halo_wait_ms": r_[2], "stencil_ms": r_[0] - r_[2]}
+                                           for i, r_ in enumerate(per_rank)] if per_rank else None),
+                "roofline": roof,
+                "kernels": kern,
+                "finite": finite,
+                "swh_norm_rank0": {"avg": swh_avg, "min": swh_min, "max": swh_max},
+            })
+        if a.full and world == 1 and not a.no_cpu_baseline:
             cng = a.cpu_baseline_grid
             if cng <= 0:
                 try:

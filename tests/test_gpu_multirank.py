@@ -42,7 +42,7 @@ def test_bench_two_ranks_on_one_gpu_match_single_rank(tmp_path, nranks, launcher
     # the compact copy handed from the first advection step to the second.
     # extra = --irefra 2: currents; on N > 1 ranks the extended environment rows come from PROENVHALO on the device (owned rows + one
     # exchange of 3 NFRE + 3 reals per halo row through the same transport), on one rank from the host assembly: same bits
-    common = ["--grid", "48", "--steps", "3", "--warmup", "1", "--no-cpu-baseline"] + extra
+    common = ["--grid", "48", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline"] + extra      # --full: finite, swh norms
     one = _run([sys.executable, "bench.py", "--gpus", "1", "--dump", str(tmp_path / "one")] + common, env)
     tail = ["bench.py", "--gpus", str(nranks), "--share-gpu", "--dump", str(tmp_path / "many")] + common
     if launcher == "self":
@@ -67,6 +67,22 @@ def test_bench_refuses_more_gpus_than_the_node_has():
     r = subprocess.run([sys.executable, "bench.py", "--gpus", str(n), "--steps", "1", "--warmup", "0", "--no-cpu-baseline"], cwd=ROOT, env=env,
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
     assert r.returncode != 0 and "visible" in r.stderr and not [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+
+
+def test_plain_bench_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """A plain `bench.py --gpus 1` times --steps steps once and prints the headline only (no kernel, roofline or CPU figures);
+    --dump-outputs writes the spectra the last step left, the same bits --dump writes (O24: every sea point fits the sample)."""
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    out = _run([sys.executable, "bench.py", "--gpus", "1", "--grid", "24", "--steps", "3", "--warmup", "1", "--dump", str(tmp_path / "all"),
+                "--dump-outputs", str(tmp_path / "out")], env)
+    assert out["steps"] == 3 and out["ms_per_step"] > 0 and out["dtype"] == "f32" and out["higher_is_better"] is True
+    assert not {"kernels", "roofline", "cpu_baseline", "window_ms", "swh_norm_rank0"} & set(out)
+    fl = np.load(str(tmp_path / "all") + ".0.npy")
+    got = {f: np.load(str(tmp_path / "out" / f"{f}.npy")) for f in ("fl1", "xllws", "ff", "intf", "mij")}
+    assert np.array_equal(got["fl1"], fl) and all(a.shape[0] == fl.shape[0] for a in got.values())
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in got.values())
 
 
 def test_library_rccl_exchange_loopback_on_one_gpu(tmp_path):
@@ -136,7 +152,7 @@ def test_halo_transports_agree_between_two_devices(tmp_path):
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
-    common = ["--grid", "48", "--steps", "3", "--warmup", "1", "--repeats", "1", "--no-cpu-baseline", "--ifrelfmax", "5", "--adv-per-source", "2"]
+    common = ["--grid", "48", "--steps", "3", "--warmup", "1", "--full", "--repeats", "1", "--no-cpu-baseline", "--ifrelfmax", "5", "--adv-per-source", "2"]
     outs = {}
     for halo in ("lib", "torch", "host"):
         outs[halo] = _run([sys.executable, "bench.py", "--gpus", "2", "--halo", halo, "--dump", str(tmp_path / halo)] + common, env)
@@ -175,6 +191,6 @@ def test_bench_refuses_a_counter_summary_of_another_workload():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     pmc = os.path.join(ROOT, "profiles", "r05_bench_O320_sp_pmc.json")
     assert os.path.exists(pmc)
-    r = subprocess.run([sys.executable, "bench.py", "--grid", "48", "--steps", "1", "--warmup", "0", "--repeats", "1", "--no-cpu-baseline", "--pmc-file", pmc],
+    r = subprocess.run([sys.executable, "bench.py", "--grid", "48", "--steps", "1", "--warmup", "0", "--full", "--repeats", "1", "--no-cpu-baseline", "--pmc-file", pmc],
                        cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
     assert r.returncode != 0 and "refused" in r.stderr and not [ln for ln in r.stdout.splitlines() if ln.startswith("{")], r.stderr[-400:]

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Counter summary of the bench kernels, taken on the bench command itself (so that the summary describes the grid, spectrum and precision the
-bench line is quoted on): rocprofv3 --pmc passes over `python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline <args>`, each counter set in its
+bench line is quoted on): rocprofv3 --pmc passes over `python3 bench.py --steps 3 --warmup 1 --full --no-cpu-baseline <args>`, each counter set in its
 own pass (MI355X_MICROARCH.md: 8 SQ slots per pass, FETCH_SIZE and WRITE_SIZE do not fit one pass), kernel-trace only beside --pmc.
 
 python3 tools/pmc_bench.py out.json [bench.py arguments ...]
@@ -29,7 +29,7 @@ shutil.rmtree(work, ignore_errors=True)
 os.makedirs(work)
 os.chdir(ROOT)
 env = dict(os.environ, TMPDIR="/tmp")
-cmd = ["python3", "bench.py", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", *bench_args]
+cmd = ["python3", "bench.py", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline", *bench_args]
 r = subprocess.run(cmd, capture_output=True, text=True, env=env)
 line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
 if r.returncode != 0 or not line:

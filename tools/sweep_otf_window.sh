@@ -5,6 +5,6 @@ export ECWAM_HIP_LIB=${GRAFT_REPO_ROOT:?GRAFT_REPO_ROOT not set}/ecwam_amd/lib/l
 for W in 0 32 64 128; do
   for G in 256 512 1024 2048 4096; do
     echo -n "strip $W grid $G: "
-    ECWAM_HIP_OTF_GRID=$G python3 bench.py --steps 10 --warmup 2 --strip $W --no-cpu-baseline 2>/dev/null | python3 -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('propags2 ms', round(d['kernels']['propags2']['ms'],3), 'step ms', round(d['ms_per_step'],3))"
+    ECWAM_HIP_OTF_GRID=$G python3 bench.py --steps 10 --warmup 2 --strip $W --full --no-cpu-baseline 2>/dev/null | python3 -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('propags2 ms', round(d['kernels']['propags2']['ms'],3), 'step ms', round(d['ms_per_step'],3))"
   done
 done
