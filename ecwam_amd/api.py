@@ -16,6 +16,9 @@ from . import lib as _lib
 from .tables import Tables
 
 NFF, NINTF, NWPR = 16, 16, 5
+# columns of ecwam_hip_outbs_sepwisw (include/ecwam_hip.h): OUTBLOCK parameters 20-22, 11-16, 23-28
+OUTBS_SEP_FIELDS = ("mp1", "mp2", "wdw", "shww", "shts", "mdww", "mdts", "mpww", "mpts",
+                    "p1sea", "p1swell", "p2sea", "p2swell", "sprdsea", "sprdswell")
 
 
 class EcwamHipError(RuntimeError):
@@ -293,6 +296,17 @@ class HipContext:
             raise ValueError("OUTBS: KIJS/KIJL outside the operands")
         self._chk(self.lib.ecwam_hip_outbs(self._h, kijs, kijl, self._real(fl1, (nrow, self.NANG, self.NFRE), "FL1"), float(zmiss),
                                            self._real(out, (out.shape[0], 5), "OUT"), _stream_ptr()))
+
+    def outbs_sepwisw(self, kijs, kijl, fl1, xllws, wvprpt, ff, out, zmiss: float = -999.0, small_domain: bool = False):
+        """Wind sea / swell and mean-period / spread parameters (ecwam_hip_outbs_sepwisw) of rows [kijs, kijl) into out[:, 15], columns
+        OUTBS_SEP_FIELDS.  small_domain: CLDOMAIN = 's' (the first wind-sea mask only)."""
+        nrow = fl1.shape[0]
+        if not (0 <= kijs <= kijl <= min(nrow, xllws.shape[0], wvprpt.shape[0], ff.shape[0], out.shape[0])):
+            raise ValueError("OUTBS_SEPWISW: KIJS/KIJL outside the operands")
+        a = [self._real(fl1, (nrow, self.NANG, self.NFRE), "FL1"), self._real(xllws, (xllws.shape[0], self.NANG, self.NFRE), "XLLWS"),
+             self._real(wvprpt, (wvprpt.shape[0], NWPR, self.NFRE), "WVPRPT"), self._real(ff, (ff.shape[0], NFF), "FF")]
+        self._chk(self.lib.ecwam_hip_outbs_sepwisw(self._h, kijs, kijl, *a, 1 if small_domain else 0, float(zmiss),
+                                                   self._real(out, (out.shape[0], len(OUTBS_SEP_FIELDS)), "OUT"), _stream_ptr()))
 
     def outwnorm(self, field, column: int, n: int, zmiss: float = -999.0):
         """(average, minimum, maximum, count) of field[:n, column] over the values != zmiss."""

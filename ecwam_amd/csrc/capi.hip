@@ -80,6 +80,8 @@ template <typename T> void launch_propags2_gen(const void*, int, const void*, vo
 template <typename T> void launch_propags2_otf(const void*, const void*, void*, int, int, double, const int*, const void*, double, const void*, const void*, const int*, const int*, const int*, const void*, const void*, const void*, const void*, const int*, int, int, int, int, int, int, const void*, int, double, int, void*, int, const void*, int, int, hipStream_t);
 template <typename T> void launch_copy_freq_range(const void*, void*, int, int, int, int, int, int, hipStream_t);
 template <typename T> int launch_outbs(const void*, int, int, const void*, double, void*, int, int, hipStream_t);
+template <typename T> int launch_outbs_sepwisw(const void*, int, int, const void*, const void*, const void*, const void*, int, double, void*, int, int,
+                                               hipStream_t);
 template <typename T> void launch_norm(const void*, int, int, double, double*, int, hipStream_t);
 template <typename T> void launch_newwind(const void*, int, void*, const void*, int, hipStream_t);
 template <typename T> void launch_nosource(const void*, int, int, int, void*, void*, int*, hipStream_t);
@@ -910,6 +912,21 @@ int ecwam_hip_outbs(ecwam_hip_ctx* c, int kijs, int kijl, const void* fl1, doubl
   DISPATCH(rc = launch_outbs<float>(c->dtab, kijs, kijl, fl1, zmiss, out, c->NANG, c->NFRE, s),
            rc = launch_outbs<double>(c->dtab, kijs, kijl, fl1, zmiss, out, c->NANG, c->NFRE, s));
   if (rc) return fail("ecwam_hip_outbs: unsupported spectral size");
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+int ecwam_hip_outbs_sepwisw(ecwam_hip_ctx* c, int kijs, int kijl, const void* fl1, const void* xllws, const void* wvprpt, const void* ff, int flags,
+                            double zmiss, void* out, void* stream) {
+  if (!c) return fail("null context");
+  if (kijl < kijs || kijs < 0) return fail("ecwam_hip_outbs_sepwisw: bad range");
+  if (kijl > kijs && (!fl1 || !xllws || !wvprpt || !ff || !out)) return fail("ecwam_hip_outbs_sepwisw: null pointer");
+  if (flags & ~1) return fail("ecwam_hip_outbs_sepwisw: unknown flags");
+  hipStream_t s = (hipStream_t)stream;
+  int rc;
+  DISPATCH(rc = launch_outbs_sepwisw<float>(c->dtab, kijs, kijl, fl1, xllws, wvprpt, ff, flags, zmiss, out, c->NANG, c->NFRE, s),
+           rc = launch_outbs_sepwisw<double>(c->dtab, kijs, kijl, fl1, xllws, wvprpt, ff, flags, zmiss, out, c->NANG, c->NFRE, s));
+  if (rc) return fail("ecwam_hip_outbs_sepwisw: unsupported spectral size");
   HIPCHK(hipGetLastError());
   return 0;
 }

@@ -16,6 +16,8 @@ import torch
 from . import api, decomp, synthetic as syn
 from .tables import Config, Tables
 
+OUTBS_SEP_FIELDS = api.OUTBS_SEP_FIELDS     # the columns of Wamintgr.outbs_sepwisw()
+
 
 class HaloExchange:
     """MPEXCHNG (mpexchng.F90:141-206): pack -> point-to-point exchange with the neighbouring ranks -> halo rows.
@@ -578,6 +580,12 @@ class Wamintgr:
     def outbs(self) -> torch.Tensor:
         out = torch.zeros((self.n, 5), dtype=self.dtype, device=self.dev)
         self.ctx.outbs(0, self.n, self.fl1, out)
+        return out
+
+    # ---- wind sea / swell and mean-period / spread parameters on the device: [n][15], columns api.OUTBS_SEP_FIELDS
+    def outbs_sepwisw(self, small_domain: bool = False) -> torch.Tensor:
+        out = torch.zeros((self.n, len(api.OUTBS_SEP_FIELDS)), dtype=self.dtype, device=self.dev)
+        self.ctx.outbs_sepwisw(0, self.n, self.fl1, self.xllws, self.wvprpt, self.ff, out, small_domain=small_domain)
         return out
 
     def swh_norm(self):

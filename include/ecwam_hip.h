@@ -332,6 +332,24 @@ int ecwam_hip_propags2_implsch(ecwam_hip_ctx *ctx, const void *f1, void *f3, int
 int ecwam_hip_outbs(ecwam_hip_ctx *ctx, int kijs, int kijl, const void *fl1, double zmiss, void *out, void *stream);
 int ecwam_hip_outwnorm(ecwam_hip_ctx *ctx, const void *field, int stride, int n, double zmiss, double *result, void *stream);
 
+/*
+ * Wind sea / swell and the mean-period / spread parameters of OUTBLOCK (outblock.F90:214-382 with FL2ND = FL1: IREFRA 0/1,
+ * LSECONDORDER = F, no LICERUN noise reshaping, no OUTSETWMASK) for rows [kijs,kijl): SEPWISW (sepwisw.F90) with LLPARTITION = F --
+ * the wind-sea mask from xllws (the XLLWS of ecwam_hip_implsch), CINV = wvprpt[ij][2][:], UFRIC = ff[ij][7] and WDWAVE = ff[ij][1],
+ * then FEMEAN, STHQ, MWP1, MWP2 and WDIRSPREAD (LLPEAKF = T) of the swell and of the wind-sea part -- and MWP1, MWP2, WDIRSPREAD
+ * (LLPEAKF = F) of the total spectrum.  Swell trains (SEP3TR, parameters 42-50) are not computed; MIJ and WSWAVE are not read.
+ * out[npts][15] (columns; OUTBLOCK parameter numbers in brackets):
+ *    0 mp1   MWP1 of the total spectrum [20]        1 mp2   MWP2 [21]        2 wdw   WDIRSPREAD [22]
+ *    3 shww  wind-sea height 4*SQRT(MAX(ESEA,0)) [11]                        4 shts  swell height 4*SQRT(MAX(ESWELL,0)) [12]
+ *    5 mdww  wind-sea direction, degrees, MOD(DEG*THWISEA+180,360) [13]      6 mdts  swell direction [14]
+ *    7 mpww  wind-sea mean period 1/FSEA or zmiss [15]                       8 mpts  swell mean period 1/FSWELL or zmiss [16]
+ *    9 P1SEA [23]  10 P1SWELL [24]  11 P2SEA [25]  12 P2SWELL [26]  13 SPRDSEA [27]  14 SPRDSWELL [28]
+ * flags: bit 0 -- CLDOMAIN = 's' (a small domain): the first mask only, without the R test, the second mask and the walk over
+ * frequencies (sepwisw.F90:177).  OUTWNORM statistics of a column: ecwam_hip_outwnorm(out + column, stride = 15).
+ */
+int ecwam_hip_outbs_sepwisw(ecwam_hip_ctx *ctx, int kijs, int kijl, const void *fl1, const void *xllws, const void *wvprpt, const void *ff,
+                            int flags, double zmiss, void *out, void *stream);
+
 /* NEWWIND forcing hand-over (newwind.F90:126-161): FF <- FF_NEXT members + TAUW cap.  ecwam_hip_newwind takes ICODE_WND = ICODE
  * of the parameters; a coupled host (LWCOU) passes ICODE_CPL through ecwam_hip_newwind_icode (newwind.F90:120-124). */
 int ecwam_hip_newwind(ecwam_hip_ctx *ctx, int n, void *ff, const void *ff_next, void *stream);
