@@ -19,6 +19,8 @@ NFF, NINTF, NWPR = 16, 16, 5
 # columns of ecwam_hip_outbs_sepwisw (include/ecwam_hip.h): OUTBLOCK parameters 20-22, 11-16, 23-28
 OUTBS_SEP_FIELDS = ("mp1", "mp2", "wdw", "shww", "shts", "mdww", "mdts", "mpww", "mpts",
                     "p1sea", "p1swell", "p2sea", "p2swell", "sprdsea", "sprdswell")
+# columns of ecwam_hip_outbs_extremes (include/ecwam_hip.h): OUTBLOCK parameters 29, 30, 31, 33, 34, 57, 70, 71, 72 (KURTOSIS), 78-81 (W_MAXH)
+OUTBS_EXT_FIELDS = ("c4", "bfi", "qp", "hmax", "tmax", "c3", "eta_m", "r", "xnslc", "cmax_f", "hmax_n", "cmax_st", "hmax_st")
 
 
 class EcwamHipError(RuntimeError):
@@ -307,6 +309,17 @@ class HipContext:
              self._real(wvprpt, (wvprpt.shape[0], NWPR, self.NFRE), "WVPRPT"), self._real(ff, (ff.shape[0], NFF), "FF")]
         self._chk(self.lib.ecwam_hip_outbs_sepwisw(self._h, kijs, kijl, *a, 1 if small_domain else 0, float(zmiss),
                                                    self._real(out, (out.shape[0], len(OUTBS_SEP_FIELDS)), "OUT"), _stream_ptr()))
+
+    def outbs_extremes(self, kijs, kijl, fl1, wvprpt, ff, out, kurtosis_only: bool = False):
+        """Extreme-wave parameters (ecwam_hip_outbs_extremes: KURTOSIS and W_MAXH) of rows [kijs, kijl) into out[:, 13], columns
+        OUTBS_EXT_FIELDS.  kurtosis_only: W_MAXH skipped, columns 9-12 left as they are."""
+        nrow = fl1.shape[0]
+        if not (0 <= kijs <= kijl <= min(nrow, wvprpt.shape[0], ff.shape[0], out.shape[0])):
+            raise ValueError("OUTBS_EXTREMES: KIJS/KIJL outside the operands")
+        a = [self._real(fl1, (nrow, self.NANG, self.NFRE), "FL1"), self._real(wvprpt, (wvprpt.shape[0], NWPR, self.NFRE), "WVPRPT"),
+             self._real(ff, (ff.shape[0], NFF), "FF")]
+        self._chk(self.lib.ecwam_hip_outbs_extremes(self._h, kijs, kijl, *a, 1 if kurtosis_only else 0,
+                                                    self._real(out, (out.shape[0], len(OUTBS_EXT_FIELDS)), "OUT"), _stream_ptr()))
 
     def outwnorm(self, field, column: int, n: int, zmiss: float = -999.0):
         """(average, minimum, maximum, count) of field[:n, column] over the values != zmiss."""

@@ -17,6 +17,7 @@ from . import api, decomp, synthetic as syn
 from .tables import Config, Tables
 
 OUTBS_SEP_FIELDS = api.OUTBS_SEP_FIELDS     # the columns of Wamintgr.outbs_sepwisw()
+OUTBS_EXT_FIELDS = api.OUTBS_EXT_FIELDS     # the columns of Wamintgr.outbs_extremes()
 
 
 class HaloExchange:
@@ -586,6 +587,12 @@ class Wamintgr:
     def outbs_sepwisw(self, small_domain: bool = False) -> torch.Tensor:
         out = torch.zeros((self.n, len(api.OUTBS_SEP_FIELDS)), dtype=self.dtype, device=self.dev)
         self.ctx.outbs_sepwisw(0, self.n, self.fl1, self.xllws, self.wvprpt, self.ff, out, small_domain=small_domain)
+        return out
+
+    # ---- extreme-wave parameters on the device (KURTOSIS, W_MAXH): [n][13], columns api.OUTBS_EXT_FIELDS; kurtosis_only: columns 9-12 stay 0
+    def outbs_extremes(self, kurtosis_only: bool = False) -> torch.Tensor:
+        out = torch.zeros((self.n, len(api.OUTBS_EXT_FIELDS)), dtype=self.dtype, device=self.dev)
+        self.ctx.outbs_extremes(0, self.n, self.fl1, self.wvprpt, self.ff, out, kurtosis_only=kurtosis_only)
         return out
 
     def swh_norm(self):

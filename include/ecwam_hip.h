@@ -350,6 +350,24 @@ int ecwam_hip_outwnorm(ecwam_hip_ctx *ctx, const void *field, int stride, int n,
 int ecwam_hip_outbs_sepwisw(ecwam_hip_ctx *ctx, int kijs, int kijl, const void *fl1, const void *xllws, const void *wvprpt, const void *ff,
                             int flags, double zmiss, void *out, void *stream);
 
+/*
+ * Extreme-wave parameters of OUTBLOCK for rows [kijs,kijl): KURTOSIS (kurtosis.F90 with PEAK_ANG, AKI, TRANSF_BFI, STAT_NL, TRANSF_R,
+ * H_MAX; outblock.F90:208-211, called at every output time) and W_MAXH (w_maxh.F90 with W_MODE_ST; outblock.F90:559-578).  Inputs:
+ * fl1 (FL1), WAVNUM = wvprpt[ij][0][:], DEPTH = ff[ij][15] (ENVIRONMENT%DEPTH).  out[npts][13] indexed by the absolute row ij
+ * (columns; OUTBLOCK parameter numbers with NTRAIN = 3, NTEWH = 6 in brackets):
+ *    0 c4     kurtosis C4 [29]                 1 bfi    BF2, square of the Benjamin-Feir index [30]     2 qp    Goda peakedness QP [31]
+ *    3 hmax   envelope maximum height HMAX [33]   4 tmax   period of the maximum TMAX [34]            5 c3    skewness C3 [57]
+ *    6 eta_m  wave-induced sea-level correction ETA_M [70]   7 r   spectral width index R [71]     8 xnslc number of events XNSLC [72]
+ *    9 cmax_f  time-domain maximum crest CMAX_F [78]         10 hmax_n  time-domain maximum height HMAX_N [79]
+ *   11 cmax_st space-time maximum crest CMAX_ST [80]         12 hmax_st space-time maximum height HMAX_ST [81]
+ * flags: bit 0 -- KURTOSIS only: W_MAXH is skipped and columns 9-12 are not written (the reference calls W_MAXH only when one of
+ * 78-81 is requested).  Other bits: error.  AKI's open iteration is bounded at 100 Newton steps.  Not served: the FL2ND transforms
+ * (INTPOL, LSECONDORDER; KURTOSIS and W_MAXH read FL1), OUTSETWMASK, SIG_TH / EPS / XNU and PHIST (not OUTBLOCK parameters).
+ * OUTWNORM statistics of a column: ecwam_hip_outwnorm(out + column, stride = 13).
+ */
+int ecwam_hip_outbs_extremes(ecwam_hip_ctx *ctx, int kijs, int kijl, const void *fl1, const void *wvprpt, const void *ff, int flags,
+                             void *out, void *stream);
+
 /* NEWWIND forcing hand-over (newwind.F90:126-161): FF <- FF_NEXT members + TAUW cap.  ecwam_hip_newwind takes ICODE_WND = ICODE
  * of the parameters; a coupled host (LWCOU) passes ICODE_CPL through ecwam_hip_newwind_icode (newwind.F90:120-124). */
 int ecwam_hip_newwind(ecwam_hip_ctx *ctx, int n, void *ff, const void *ff_next, void *stream);
