@@ -19,6 +19,8 @@ NFF, NINTF, NWPR = 16, 16, 5
 # columns of ecwam_hip_outbs_sepwisw (include/ecwam_hip.h): OUTBLOCK parameters 20-22, 11-16, 23-28
 OUTBS_SEP_FIELDS = ("mp1", "mp2", "wdw", "shww", "shts", "mdww", "mdts", "mpww", "mpts",
                     "p1sea", "p1swell", "p2sea", "p2swell", "sprdsea", "sprdswell")
+# columns of ecwam_hip_outbs_partition (include/ecwam_hip.h): those of ecwam_hip_outbs_sepwisw, then the swell trains 1-3 (parameters 42-50)
+OUTBS_PART_FIELDS = OUTBS_SEP_FIELDS + ("swh1", "mwd1", "mwp1", "swh2", "mwd2", "mwp2", "swh3", "mwd3", "mwp3")
 # columns of ecwam_hip_outbs_extremes (include/ecwam_hip.h): OUTBLOCK parameters 29, 30, 31, 33, 34, 57, 70, 71, 72 (KURTOSIS), 78-81 (W_MAXH)
 OUTBS_EXT_FIELDS = ("c4", "bfi", "qp", "hmax", "tmax", "c3", "eta_m", "r", "xnslc", "cmax_f", "hmax_n", "cmax_st", "hmax_st")
 
@@ -309,6 +311,18 @@ class HipContext:
              self._real(wvprpt, (wvprpt.shape[0], NWPR, self.NFRE), "WVPRPT"), self._real(ff, (ff.shape[0], NFF), "FF")]
         self._chk(self.lib.ecwam_hip_outbs_sepwisw(self._h, kijs, kijl, *a, 1 if small_domain else 0, float(zmiss),
                                                    self._real(out, (out.shape[0], len(OUTBS_SEP_FIELDS)), "OUT"), _stream_ptr()))
+
+    def outbs_partition(self, kijs, kijl, fl1, xllws, mij, wvprpt, ff, out, zmiss: float = -999.0, flags: int = 0):
+        """Swell-train partitioning (ecwam_hip_outbs_partition: SEPWISW with LLPARTITION = T) of rows [kijs, kijl) into out[:, 24], columns
+        OUTBS_PART_FIELDS.  mij: the int32 MIJ of implsch() (1-based).  flags: 0 only (the library refuses every bit)."""
+        nrow = fl1.shape[0]
+        if not (0 <= kijs <= kijl <= min(nrow, xllws.shape[0], mij.shape[0], wvprpt.shape[0], ff.shape[0], out.shape[0])):
+            raise ValueError("OUTBS_PARTITION: KIJS/KIJL outside the operands")
+        a = [self._real(fl1, (nrow, self.NANG, self.NFRE), "FL1"), self._real(xllws, (xllws.shape[0], self.NANG, self.NFRE), "XLLWS"),
+             self._int(mij, (mij.shape[0],), "MIJ"), self._real(wvprpt, (wvprpt.shape[0], NWPR, self.NFRE), "WVPRPT"),
+             self._real(ff, (ff.shape[0], NFF), "FF")]
+        self._chk(self.lib.ecwam_hip_outbs_partition(self._h, kijs, kijl, *a, int(flags), float(zmiss),
+                                                     self._real(out, (out.shape[0], len(OUTBS_PART_FIELDS)), "OUT"), _stream_ptr()))
 
     def outbs_extremes(self, kijs, kijl, fl1, wvprpt, ff, out, kurtosis_only: bool = False):
         """Extreme-wave parameters (ecwam_hip_outbs_extremes: KURTOSIS and W_MAXH) of rows [kijs, kijl) into out[:, 13], columns

@@ -82,6 +82,8 @@ template <typename T> void launch_copy_freq_range(const void*, void*, int, int, 
 template <typename T> int launch_outbs(const void*, int, int, const void*, double, void*, int, int, hipStream_t);
 template <typename T> int launch_outbs_sepwisw(const void*, int, int, const void*, const void*, const void*, const void*, int, double, void*, int, int,
                                                hipStream_t);
+template <typename T> int launch_outbs_partition(const void*, int, int, const void*, const void*, const int*, const void*, const void*, double, void*, int,
+                                                  int, hipStream_t);
 template <typename T> int launch_outbs_extremes(const void*, int, int, const void*, const void*, const void*, int, void*, int, int, hipStream_t);
 template <typename T> void launch_norm(const void*, int, int, double, double*, int, hipStream_t);
 template <typename T> void launch_newwind(const void*, int, void*, const void*, int, hipStream_t);
@@ -928,6 +930,23 @@ int ecwam_hip_outbs_sepwisw(ecwam_hip_ctx* c, int kijs, int kijl, const void* fl
   DISPATCH(rc = launch_outbs_sepwisw<float>(c->dtab, kijs, kijl, fl1, xllws, wvprpt, ff, flags, zmiss, out, c->NANG, c->NFRE, s),
            rc = launch_outbs_sepwisw<double>(c->dtab, kijs, kijl, fl1, xllws, wvprpt, ff, flags, zmiss, out, c->NANG, c->NFRE, s));
   if (rc) return fail("ecwam_hip_outbs_sepwisw: unsupported spectral size");
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+int ecwam_hip_outbs_partition(ecwam_hip_ctx* c, int kijs, int kijl, const void* fl1, const void* xllws, const int* mij, const void* wvprpt,
+                              const void* ff, int flags, double zmiss, void* out, void* stream) {
+  if (!c) return fail("null context");
+  if (kijl < kijs || kijs < 0) return fail("ecwam_hip_outbs_partition: bad range");
+  if (kijl > kijs && (!fl1 || !xllws || !mij || !wvprpt || !ff || !out)) return fail("ecwam_hip_outbs_partition: null pointer");
+  if (flags & 1)
+    return fail("ecwam_hip_outbs_partition: CLDOMAIN = 's' (flags bit 0) is not supported: SEP3TR would read an FSEA that SEPWISW has not computed");
+  if (flags) return fail("ecwam_hip_outbs_partition: unknown flags");
+  hipStream_t s = (hipStream_t)stream;
+  int rc;
+  DISPATCH(rc = launch_outbs_partition<float>(c->dtab, kijs, kijl, fl1, xllws, mij, wvprpt, ff, zmiss, out, c->NANG, c->NFRE, s),
+           rc = launch_outbs_partition<double>(c->dtab, kijs, kijl, fl1, xllws, mij, wvprpt, ff, zmiss, out, c->NANG, c->NFRE, s));
+  if (rc) return fail("ecwam_hip_outbs_partition: unsupported spectral size");
   HIPCHK(hipGetLastError());
   return 0;
 }

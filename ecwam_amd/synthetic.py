@@ -158,3 +158,44 @@ def obstructions(grid, nfre: int, seed: int = 99, fraction: float = 0.25):
     val = 1.0 - (1.0 - base[:, :, None]) * (0.5 + 0.5 * ramp)
     obs[hit] = val[hit]
     return obs
+
+
+def multi_system_spectra(fr, th, wdwave, dtype, seed: int = 0, max_swells: int = 4, epsmin=0.1e-32):
+    """FL1[ij][k][m]: a wind sea along WDWAVE plus 0 .. max_swells swell systems per point, each with a random peak frequency, direction,
+    directional spread and energy; reproducible by seed.  The workload of the swell-train partitioning (SEP3TR): several separated
+    maxima in the swell part of the spectrum.  Returns (FL1, systems) with systems[ij] = list of (fp, direction, alfa) of the swells."""
+    wdwave = np.asarray(wdwave, np.float64)
+    n = wdwave.size
+    rng = np.random.default_rng(seed)
+    frd = np.asarray(fr, np.float64)
+    thd = np.asarray(th, np.float64)
+    fl = jonswap_spectra(frd, thd, rng.uniform(0.12, 0.3, n), wdwave, np.float64, epsmin=0.0)
+    nsw = rng.integers(0, max_swells + 1, n)
+    systems = [[] for _ in range(n)]
+    g, zpi = 9.806, 2 * np.pi
+    for j in range(max_swells):
+        fp = rng.uniform(0.045, 0.12, n)
+        dr = rng.uniform(0.0, zpi, n)
+        alfa = 10.0 ** rng.uniform(-3.3, -2.2, n)
+        s = rng.uniform(2.0, 12.0, n)                                      # cos**(2s) spread
+        has = nsw > j
+        fa = frd[None, :]
+        e = alfa[:, None] * g * g / zpi ** 4 * fa ** -5.0 * np.exp(-1.25 * (fp[:, None] / fa) ** 4) * 3.0 ** np.exp(
+            -0.5 * ((fa - fp[:, None]) / (0.07 * fp[:, None])) ** 2)
+        c = np.maximum(0.0, np.cos(thd[None, :] - dr[:, None])) ** (2 * s[:, None])
+        c = c / np.maximum(c.sum(1, keepdims=True) * (zpi / thd.size), 1e-30)
+        fl += np.where(has[:, None, None], c[:, :, None] * e[:, None, :], 0.0)
+        for i in np.nonzero(has)[0]:
+            systems[i].append((fp[i], dr[i], alfa[i]))
+    return np.maximum(fl, epsmin).astype(dtype), systems
+
+
+def many_peak_spectra(fr, th, n: int, dtype, amp: float = 1e-2):
+    """The worst case of the partitioning: a swell spectrum with a local maximum at every other direction of every other frequency
+    (far more than SEP3TR's 20), above the noise level everywhere.  FL1[n][k][m]."""
+    k = np.arange(len(th))[:, None]
+    m = np.arange(len(fr))[None, :]
+    hi = (k % 2 == 0) & (m % 2 == 1)
+    base = amp * (1.0 + 0.01 * np.arange(n)[:, None, None] / max(n, 1))
+    fl = base * np.where(hi, 1.0, 0.4)[None] * (1.0 + 0.001 * (k + m))[None]
+    return fl.astype(dtype)

@@ -18,6 +18,7 @@ from .tables import Config, Tables
 
 OUTBS_SEP_FIELDS = api.OUTBS_SEP_FIELDS     # the columns of Wamintgr.outbs_sepwisw()
 OUTBS_EXT_FIELDS = api.OUTBS_EXT_FIELDS     # the columns of Wamintgr.outbs_extremes()
+OUTBS_PART_FIELDS = api.OUTBS_PART_FIELDS   # the columns of Wamintgr.outbs_partition()
 
 
 class HaloExchange:
@@ -587,6 +588,12 @@ class Wamintgr:
     def outbs_sepwisw(self, small_domain: bool = False) -> torch.Tensor:
         out = torch.zeros((self.n, len(api.OUTBS_SEP_FIELDS)), dtype=self.dtype, device=self.dev)
         self.ctx.outbs_sepwisw(0, self.n, self.fl1, self.xllws, self.wvprpt, self.ff, out, small_domain=small_domain)
+        return out
+
+    # ---- swell-train partitioning on the device (SEPWISW with LLPARTITION = T): [n][24], columns api.OUTBS_PART_FIELDS
+    def outbs_partition(self) -> torch.Tensor:
+        out = torch.zeros((self.n, len(api.OUTBS_PART_FIELDS)), dtype=self.dtype, device=self.dev)
+        self.ctx.outbs_partition(0, self.n, self.fl1, self.xllws, self.mij, self.wvprpt, self.ff, out)
         return out
 
     # ---- extreme-wave parameters on the device (KURTOSIS, W_MAXH): [n][13], columns api.OUTBS_EXT_FIELDS; kurtosis_only: columns 9-12 stay 0

@@ -337,7 +337,9 @@ int ecwam_hip_outwnorm(ecwam_hip_ctx *ctx, const void *field, int stride, int n,
  * LSECONDORDER = F, no LICERUN noise reshaping, no OUTSETWMASK) for rows [kijs,kijl): SEPWISW (sepwisw.F90) with LLPARTITION = F --
  * the wind-sea mask from xllws (the XLLWS of ecwam_hip_implsch), CINV = wvprpt[ij][2][:], UFRIC = ff[ij][7] and WDWAVE = ff[ij][1],
  * then FEMEAN, STHQ, MWP1, MWP2 and WDIRSPREAD (LLPEAKF = T) of the swell and of the wind-sea part -- and MWP1, MWP2, WDIRSPREAD
- * (LLPEAKF = F) of the total spectrum.  Swell trains (SEP3TR, parameters 42-50) are not computed; MIJ and WSWAVE are not read.
+ * (LLPEAKF = F) of the total spectrum.  Swell trains (SEP3TR, parameters 42-50) are not computed; MIJ and WSWAVE are not read.  When any
+ * of 42-50 is requested the reference runs SEPWISW with LLPARTITION = T: use ecwam_hip_outbs_partition instead, whose columns 0-14 are
+ * these columns as that configuration computes them.
  * out[npts][15] (columns; OUTBLOCK parameter numbers in brackets):
  *    0 mp1   MWP1 of the total spectrum [20]        1 mp2   MWP2 [21]        2 wdw   WDIRSPREAD [22]
  *    3 shww  wind-sea height 4*SQRT(MAX(ESEA,0)) [11]                        4 shts  swell height 4*SQRT(MAX(ESWELL,0)) [12]
@@ -349,6 +351,22 @@ int ecwam_hip_outwnorm(ecwam_hip_ctx *ctx, const void *field, int stride, int n,
  */
 int ecwam_hip_outbs_sepwisw(ecwam_hip_ctx *ctx, int kijs, int kijl, const void *fl1, const void *xllws, const void *wvprpt, const void *ff,
                             int flags, double zmiss, void *out, void *stream);
+
+/*
+ * Swell-train partitioning of OUTBLOCK (parameters 42-50; outblock.F90:214-382, 436-449 with FL2ND = FL1) for rows [kijs,kijl): SEPWISW
+ * with LLPARTITION = T -- SEP3TR, FNDPRT and PARMEAN after the wind-sea / swell split of ecwam_hip_outbs_sepwisw.  Inputs as there, plus
+ * mij (the 1-based MIJ of ecwam_hip_implsch; SEP3TR looks for peaks below it and drops partitions of mean period under INT(1/FR(MIJ))).
+ * WSWAVE is not read.  out[npts][24] indexed by the absolute row ij: columns 0-14 those of ecwam_hip_outbs_sepwisw, as the reference
+ * computes them with LLPARTITION = T (FNDPRT's factor MAX(W1,1) on the swell mask is 1, so they equal the LLPARTITION = F values), then
+ * for the swell trains ITR = 1..3 (OUTBLOCK parameter numbers in brackets):
+ *   15 + 3(ITR-1) swh  4*SQRT(MAX(EMTRAIN,0)) [42 + 3(ITR-1)]     16 + 3(ITR-1) mwd  MOD(DEG*THTRAIN+180,360) [43 + ...]
+ *   17 + 3(ITR-1) mwp  PMTRAIN [44 + ...], 0 where there is no train (no zmiss, as outblock.F90:436-449)
+ * A point has at most NPMAX = 20 peaks (in order of discovery, M-major) and at most 25 sweeps per peak.  flags: 0 only; bit 0 (CLDOMAIN =
+ * 's') is refused -- the reference hands SEP3TR an FSEA it has not computed in that branch -- and so is every other bit.  The spectral
+ * sizes of ecwam_hip_outbs_sepwisw.  OUTWNORM statistics of a column: ecwam_hip_outwnorm(out + column, stride = 24).
+ */
+int ecwam_hip_outbs_partition(ecwam_hip_ctx *ctx, int kijs, int kijl, const void *fl1, const void *xllws, const int *mij, const void *wvprpt,
+                              const void *ff, int flags, double zmiss, void *out, void *stream);
 
 /*
  * Extreme-wave parameters of OUTBLOCK for rows [kijs,kijl): KURTOSIS (kurtosis.F90 with PEAK_ANG, AKI, TRANSF_BFI, STAT_NL, TRANSF_R,

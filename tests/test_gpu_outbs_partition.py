@@ -1,0 +1,260 @@
+"""Swell-train partitioning of OUTBLOCK on the device (ecwam_hip_outbs_partition) against the numpy restatement tests/partition_ref.py
+on the same FL1 / XLLWS / MIJ / CINV / FF.
+
+Gates.  Every point (but those below) must have as many non-zero trains as the restatement.  Heights and periods relative, directions
+cyclic in degrees, spreads absolute (SP_GATES / DP_GATES: at most 10 x the observed maxima, which each test prints); in double precision
+also 1e-12 relative on every column (directions: of 360 degrees, where the part or train carries energy).  As in
+test_gpu_outbs_sepwisw.py, points where the restatement finds a CHECKTA within 4 ulp of 1 are counted and left out, and so are the points
+where one of SEP3TR's scalar decisions (EUNASNG > SUMENE, the HSMIN and period tests, FSWELL < FSEA of the fall-back) compares two sums
+within 64 ulp of each other, which the device adds in another order (together at most 0.5 % of the points); a direction is compared
+where its part or train is above 1e-3 m.
+"""
+import numpy as np
+import pytest
+
+import harness as H
+import partition_ref as P
+from ecwam_amd import synthetic as syn
+from ecwam_amd.tables import Config, Tables
+
+pytestmark = pytest.mark.gpu
+
+torch = pytest.importorskip("torch")
+
+COL = {f: i for i, f in enumerate(P.FIELDS)}
+HEIGHTS_PERIODS = ("mp1", "mp2", "shww", "shts", "mpww", "mpts", "p1sea", "p1swell", "p2sea", "p2swell",
+                   "swh1", "mwp1", "swh2", "mwp2", "swh3", "mwp3")
+DIRECTIONS = (("mdww", "shww"), ("mdts", "shts"), ("mwd1", "swh1"), ("mwd2", "swh2"), ("mwd3", "swh3"))
+SPREADS = ("wdw", "sprdsea", "sprdswell")
+# observed maxima over every test of this file (after IMPLSCH at 36 / 24 / 48 x 36, 12 x 25, the known answers, every point at NPMAX,
+# O48 after four steps):
+#   sp: heights / periods 8.8e-7 relative, directions 7.5e-4 degrees, spreads 5.5e-6
+#   dp: heights / periods 1.6e-15 relative, directions 1.2e-12 degrees, spreads 1.2e-14
+SP_GATES = dict(rel=8e-6, deg=5e-3, spread=5e-5)
+DP_GATES = dict(rel=1.5e-14, deg=1e-11, spread=1e-13)
+
+
+@pytest.fixture(scope="module")
+def api():
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    from ecwam_amd import api as _api
+
+    return _api
+
+
+def _device(ctx, *arrays):
+    return [torch.from_numpy(np.ascontiguousarray(a)).to(ctx.device) for a in arrays]
+
+
+def _run(api, ctx, fl1, xllws, mij, wv, ff, kijs=0, kijl=None, fill=-1.0, flags=0):
+    n = fl1.shape[0]
+    kijl = n if kijl is None else kijl
+    tfl, txl, twv, tff = _device(ctx, fl1, xllws, wv, ff)
+    tmij = torch.from_numpy(np.ascontiguousarray(mij, np.int32)).to(ctx.device)
+    out = torch.full((n, len(P.FIELDS)), fill, dtype=ctx.dtype, device=ctx.device)
+    ctx.outbs_partition(kijs, kijl, tfl, txl, tmij, twv, tff, out, flags=flags)
+    torch.cuda.synchronize()
+    return out.cpu().numpy()
+
+
+def _compare(got, ref, info, prec, what, sl=slice(None)):
+    near = info["near"][sl] | info["tie"][sl]
+    ok = ~near
+    assert near.mean() <= 0.005, (what, int(near.sum()))
+    g, r = got[ok].astype(np.float64), ref[ok].astype(np.float64)
+    ntr_g = (g[:, 15::3] > 0).sum(1)
+    ntr_r = (r[:, 15::3] > 0).sum(1)
+    assert np.array_equal(ntr_g, ntr_r), (what, np.nonzero(ntr_g != ntr_r)[0][:10])
+    obs = {}
+    obs["rel"] = max(float(np.max(H.rel_err(g[:, COL[c]], r[:, COL[c]], 1e-3))) for c in HEIGHTS_PERIODS)
+    dd = []
+    for c, h in DIRECTIONS:
+        live = r[:, COL[h]] > 1e-3
+        d = np.abs(g[live, COL[c]] - r[live, COL[c]]) % 360.0
+        dd.append(float(np.max(np.minimum(d, 360.0 - d))) if live.any() else 0.0)
+    obs["deg"] = max(dd)
+    obs["spread"] = max(float(np.max(np.abs(g[:, COL[c]] - r[:, COL[c]]))) for c in SPREADS)
+    print(f"{what} {prec}: points {len(near)}, CHECKTA near 1 or a near tie at {int(near.sum())}, trains per point {np.bincount(ntr_r, minlength=4)}; "
+          "observed maxima", {k: f"{v:.2e}" for k, v in obs.items()})
+    if prec == "dp":
+        live = {c: r[:, COL[h]] > 1e-3 for c, h in DIRECTIONS}
+        for c, name in enumerate(P.FIELDS):
+            sel = live.get(name, np.ones(len(r), bool))
+            e = float(np.max(H.rel_err(g[sel, c], r[sel, c], 360.0 if name in live else 1e-300), initial=0.0))
+            assert e < 1e-12, (what, name, e)
+    for k, gate in (DP_GATES if prec == "dp" else SP_GATES).items():
+        assert obs[k] < gate, (what, k, obs[k], gate)
+    return obs
+
+
+def _implsch_case(api, cfg, prec, n, seed):
+    """Multi-system spectra (a wind sea and 0-4 swells per point) through IMPLSCH on the device: FL1, XLLWS, MIJ and FF (UFRIC) of IMPLSCH,
+    CINV of the case."""
+    case = H.make_point_case(n, cfg, prec, spectra="jonswap", seed=seed)
+    t = case["tables"]
+    case["FL1"], _ = syn.multi_system_spectra(t.FR, t.TH, case["params"]["WDWAVE"][:n], t.dtype, seed=seed + 1)
+    ctx = api.HipContext(t)
+    r = H.gpu_implsch(case, ctx)
+    wv, ff, _ = H.pack_device_inputs(case)
+    ff[:, :14] = r["FF"]
+    return ctx, t, r["FL1"], r["XLLWS"], r["MIJ"], wv, ff
+
+
+@pytest.mark.parametrize("prec", ["sp", "dp"])
+@pytest.mark.parametrize("nang", [36, 24, 48])
+def test_parity_after_implsch(api, prec, nang):
+    cfg = Config(nang=nang, nfre=36, nfre_red=36)
+    n = 1501
+    ctx, t, fl1, xl, mij, wv, ff = _implsch_case(api, cfg, prec, n, seed=17)
+    assert 0 < xl.mean() < 1 and mij.min() >= 1 and mij.max() <= 36
+    got = _run(api, ctx, fl1, xl, mij, wv, ff, kijs=7, kijl=n - 3)
+    assert np.all(got[:7] == -1.0) and np.all(got[n - 3:] == -1.0)      # rows outside [kijs, kijl) untouched
+    ref, info = P.partition(t, fl1, xl, mij, wv[:, 2], ff[:, 7], ff[:, 1])
+    _compare(got[7:n - 3], ref[7:n - 3], info, prec, f"after IMPLSCH {nang}x36", slice(7, n - 3))
+    ctx.close()
+
+
+@pytest.mark.parametrize("prec", ["sp", "dp"])
+def test_parity_12x25(api, prec):
+    """12 directions (NANGH = 4 by NINT's rounding of 2.5) and an odd NFRE = 25; IMPLSCH covers 36 frequencies only, so XLLWS is the
+    synthetic rule of sepwisw_ref, MIJ random."""
+    from test_outbs_partition_host import multi_system_case
+
+    t = Tables(Config(nang=12, nfre=25, nfre_red=25), H.np_dtype(prec))
+    try:
+        ctx = api.HipContext(t)
+    except api.EcwamHipError as e:
+        pytest.fail(f"12 x 25 not accepted: {e}")
+    n = 2001
+    fl, xl, mij, cinv, uf, wd = multi_system_case(t, n, seed=23)
+    wv = np.zeros((n, 5, 25), t.dtype)
+    wv[:, 2] = cinv
+    ff = np.zeros((n, 16), t.dtype)
+    ff[:, 1], ff[:, 7] = wd, uf
+    got = _run(api, ctx, fl, xl, mij, wv, ff, kijs=7, kijl=n - 3)
+    assert np.all(got[:7] == -1.0) and np.all(got[n - 3:] == -1.0)
+    ref, info = P.partition(t, fl, xl, mij, cinv, uf, wd)
+    _compare(got[7:n - 3], ref[7:n - 3], info, prec, "12x25", slice(7, n - 3))
+    ctx.close()
+
+
+def _point_inputs(t, fl1, xl, mij, cinv, uf, wd):
+    n = len(fl1)
+    wv = np.zeros((n, 5, len(t.FR)), t.dtype)
+    wv[:, 2] = cinv
+    ff = np.zeros((n, 16), t.dtype)
+    ff[:, 1], ff[:, 7] = wd, uf
+    return wv, ff
+
+
+@pytest.mark.parametrize("prec", ["sp", "dp"])
+def test_known_answers_on_the_device(api, prec):
+    from test_outbs_partition_host import known_answer_checks, known_answer_inputs
+
+    t = Tables(Config(nang=36, nfre=36, nfre_red=36), H.np_dtype(prec))
+    names, fl1, xl, mij, cinv, uf, wd, extra = known_answer_inputs(t)
+    wv, ff = _point_inputs(t, fl1, xl, mij, cinv, uf, wd)
+    ctx = api.HipContext(t)
+    got = _run(api, ctx, fl1, xl, mij, wv, ff)
+    known_answer_checks(t, names, fl1, got, extra)
+    ref, info = P.partition(t, fl1, xl, mij, cinv, uf, wd)
+    _compare(got, ref, info, prec, "known answers")
+    ctx.close()
+
+
+@pytest.mark.parametrize("prec", ["sp", "dp"])
+def test_worst_case_every_point_at_npmax(api, prec):
+    """Every point with more than NPMAX local maxima: 20 partitions each; completes and matches the restatement."""
+    t = Tables(Config(nang=36, nfre=36, nfre_red=36), H.np_dtype(prec))
+    n = 257
+    fl = syn.many_peak_spectra(t.FR, t.TH, n, t.dtype)
+    xl = np.zeros_like(fl)
+    mij = np.full(n, 36, np.int32)
+    cinv = np.broadcast_to((t.ZPI * t.FR / t.dtype(9.806)).astype(t.dtype), (n, 36))
+    uf = np.zeros(n, t.dtype)
+    wd = np.linspace(0, 6, n).astype(t.dtype)
+    wv, ff = _point_inputs(t, fl, xl, mij, cinv, uf, wd)
+    ctx = api.HipContext(t)
+    got = _run(api, ctx, fl, xl, mij, wv, ff)
+    ref, info = P.partition(t, fl, xl, mij, cinv, uf, wd)
+    assert np.all(info["npeak_found"] > P.NPMAX) and np.all(info["npeak_fndprt"] >= P.NPMAX)
+    _compare(got, ref, info, prec, "every point at NPMAX")
+    ctx.close()
+
+
+def test_flags_are_refused(api):
+    """CLDOMAIN = 's' (bit 0) and unknown bits: the reference's SEP3TR would read an FSEA SEPWISW has not computed."""
+    t = Tables(Config(nang=36, nfre=36, nfre_red=36), np.float32)
+    ctx = api.HipContext(t)
+    n = 4
+    fl = np.full((n, 36, 36), 1e-3, np.float32)
+    wv, ff = _point_inputs(t, fl, fl * 0, np.full(n, 36), np.zeros((n, 36)), np.zeros(n), np.zeros(n))
+    for flags, msg in ((1, "CLDOMAIN"), (2, "unknown flags"), (1 << 30, "unknown flags")):
+        with pytest.raises(api.EcwamHipError, match=msg):
+            _run(api, ctx, fl, fl * 0, np.full(n, 36), wv, ff, flags=flags)
+    ctx.close()
+
+
+@pytest.mark.parametrize("prec", ["sp", "dp"])
+def test_wamintgr_on_the_o48_grid(api, prec):
+    """Four WAMINTGR steps, then Wamintgr.outbs_partition() against the restatement on the state copied back (MIJ of the last IMPLSCH);
+    its first 15 columns are Wamintgr.outbs_sepwisw()'s."""
+    from ecwam_amd import grid as G
+    from ecwam_amd.wamintgr import OUTBS_PART_FIELDS, Wamintgr
+
+    assert OUTBS_PART_FIELDS == P.FIELDS
+    cfg = Config(nang=36, nfre=36, nfre_red=36, idelt=450, idelpro=450)
+    g = G.build_grid(48, mask="continents")
+    m = Wamintgr(cfg, g, prec)
+    m.init_synthetic(seed=3)
+    assert m.build_weights() == 0
+    for _ in range(4):
+        m.step()
+    out = m.outbs_partition()
+    sep = m.outbs_sepwisw()
+    torch.cuda.synchronize()
+    n = m.n
+    assert tuple(out.shape) == (n, 24)
+    assert torch.equal(out[:, :15], sep)
+    fl = m.fl1[:n].cpu().numpy()
+    xl = m.xllws[:n].cpu().numpy()
+    mij = m.mij[:n].cpu().numpy()
+    ff = m.ff[:n].cpu().numpy()
+    wv = m.wvprpt[:n].cpu().numpy()
+    got = out.cpu().numpy()
+    ref, info = P.partition(m.t, fl, xl, mij, wv[:, 2], ff[:, 7], ff[:, 1])
+    _compare(got, ref, info, prec, "O48 after 4 steps")
+    m.ctx.close()
+
+
+def test_rows_beyond_2_32_elements(api):
+    """64-bit row addressing: FL1 / XLLWS with just over 2**32 / (NANG NFRE) rows; a case in the last 64 rows gives what it gives at row 0."""
+    cfg = Config(nang=36, nfre=36, nfre_red=36)
+    k = 64
+    ctx, t, fl1, xl, mij, wv, ff = _implsch_case(api, cfg, "sp", k, seed=31)
+    N = 36 * 36
+    rows = (2 ** 32) // N + 2 * k
+    dev, dt = ctx.device, ctx.dtype
+    want = _run(api, ctx, fl1, xl, mij, wv, ff)
+    big = {}
+    try:
+        big["fl1"] = torch.empty((rows, 36, 36), dtype=dt, device=dev)
+        big["xl"] = torch.empty((rows, 36, 36), dtype=dt, device=dev)
+        big["mij"] = torch.zeros(rows, dtype=torch.int32, device=dev)
+        big["wv"] = torch.empty((rows, 5, 36), dtype=dt, device=dev)
+        big["ff"] = torch.empty((rows, 16), dtype=dt, device=dev)
+        big["out"] = torch.full((rows, 24), -1.0, dtype=dt, device=dev)
+        a = rows - k
+        assert a * N > 2 ** 32
+        for name, arr in (("fl1", fl1), ("xl", xl), ("wv", wv), ("ff", ff), ("mij", mij.astype(np.int32))):
+            big[name][a:] = torch.from_numpy(arr).to(dev)
+        ctx.outbs_partition(a, rows, big["fl1"], big["xl"], big["mij"], big["wv"], big["ff"], big["out"])
+        torch.cuda.synchronize()
+        got = big["out"][a:].cpu().numpy()
+        assert float(big["out"][a - 1, 0]) == -1.0
+    finally:
+        big.clear()
+        torch.cuda.empty_cache()
+    assert np.array_equal(got, want)
+    ctx.close()
