@@ -387,16 +387,14 @@ struct V4Adv {
   int m0, m1;           // advected frequencies [m0, m1); the others are carried over
   int xcd_walk;         // XCD-aware order of the workgroups (diagnostics: measured 1 % slower than the natural order, profiles/r06_fused_*.txt)
 };
-#ifndef V4_ADV_DEPTH
-#define V4_ADV_DEPTH 3
-#endif
 template <typename T, int NANG, int PP, int MODE, int NSCR>
 __device__ __forceinline__ void v4_advect_tile(const V4Adv<T>& A, int ij0, int n, int lane, T* __restrict__ sT, T* __restrict__ sScr) {
   constexpr int NFRE = V4_NFRE, N = NANG * NFRE, RS = PP * NANG, VEC = 16 / (int)sizeof(T), NC = NFRE / VEC, NVL = N / VEC;
   // steps: NFULL rounds of 64 chunks per point, point after point inside a round (the chunk's direction and frequencies are then the same
   // for the PP steps of a round); the NREM chunks of every point that are left share NTS tail steps (36 directions, single precision:
-  // 324 chunks per point = 5 rounds + 4, the 12 left-over chunks of the three points are ONE step: 16 steps instead of 18)
-  constexpr int NFULL = NVL / 64, NREM = NVL - 64 * NFULL, NTS = (PP * NREM + 63) / 64, NCH = NFULL * PP + NTS, D = V4_ADV_DEPTH;
+  // 324 chunks per point = 5 rounds + 4, the 12 left-over chunks of the three points are ONE step: 16 steps instead of 18).  D: steps of
+  // gathers in flight (2, 4 and 5 measured the same as 3 in round 6: profiles/r06_fused_step_experiments.txt)
+  constexpr int NFULL = NVL / 64, NREM = NVL - 64 * NFULL, NTS = (PP * NREM + 63) / 64, NCH = NFULL * PP + NTS, NRND = NFULL + NTS, D = 3;
   constexpr int PTW = 20;                              // words per point of sPt
   typedef T VT __attribute__((ext_vector_type(VEC)));
   typedef int I4 __attribute__((ext_vector_type(4)));
@@ -438,67 +436,87 @@ __device__ __forceinline__ void v4_advect_tile(const V4Adv<T>& A, int ij0, int n
   }
   for (int i = lane; i < NANG * 4; i += 64) sD[i] = A.dirI[i];
   WSYNC();
-#if defined(V4_ADV_PRIO)
-  __builtin_amdgcn_s_setprio(V4_ADV_PRIO);      // experiment: the wave that has gathers to issue goes first on its SIMD
-#endif
   VT buf[D][NB];
-  // (point, direction, first frequency) of the lane's chunk in step c
-  auto chunk_of = [&](int c, int& q, int& k, int& m) {
+  // What a lane's chunk implies, worked out once per round -- the PP steps of a full round share direction and frequencies, a tail step is a
+  // round of its own -- and kept in registers: the tile's LDS stores between two steps would otherwise make every step read sD again and
+  // redo the division, the selectors and the offsets derived from them.
+  struct Rnd {
+    int q;                          // tail steps: the lane's point (a full round's point is the step's, the same on every lane)
+    int k, m;                       // direction, first frequency
+    int jx0, jy0, kc;               // JXO(K,1), JYO(K,1), KCR(K,1)
+    unsigned off0, off6, off7;      // bytes from the start of a source row to the chunk, and to the chunks of directions k -+ 1
+    const char* src;                // the source rows (LF: the compact rows when the chunk's frequencies are among their gin_k)
+    const char* srcl;               // src + off0: the lane's chunk in row 0
+    unsigned rnb;                   // bytes per source row
+  };
+  Rnd R[NRND];      // (indexed by compile-time rounds in the unrolled steps: registers, each live from its first gather to its last store)
+  auto round_of = [&](int c) { return c < NFULL * PP ? c / PP : NFULL + (c - NFULL * PP); };
+  auto make_round = [&](int r) {
+    Rnd o;
     int w;
-    if (c < NFULL * PP) {
-      const int it = c / PP;
-      q = c - it * PP;
-      w = lane + 64 * it;
+    o.q = 0;
+    if (r < NFULL) {
+      w = lane + 64 * r;
     } else {      // tail steps: chunk t of the PP NREM left-over ones; the lanes beyond the last one repeat it (the same stores)
-      int t = lane + 64 * (c - NFULL * PP);
+      int t = lane + 64 * (r - NFULL);
       t = t < PP * NREM ? t : PP * NREM - 1;
-      q = t / (NREM > 0 ? NREM : 1);
-      w = 64 * NFULL + (t - q * NREM);
+      o.q = t / (NREM > 0 ? NREM : 1);
+      w = 64 * NFULL + (t - o.q * NREM);
     }
-    k = w / NC;
-    m = (w - k * NC) * VEC;
-  };
-  auto issue = [&](int c, VT (&b)[NB]) {
-    int q, k, m;
-    chunk_of(c, q, k, m);
-    const I4 dk = *reinterpret_cast<const I4*>(sD + 4 * k);
-    const int jx0 = dk.x & 1, jy0 = (dk.x >> 1) & 1, kc = (dk.x >> 2) & 3;
-    const int* iq = sI + q * 16;
-    // (LF: this chunk's operands, own and neighbours, live in the compact rows when its frequencies are among their gin_k)
-    const bool fromg = LF && m < A.gin_k;
-    const T* src = fromg ? A.gin : A.f_in;
+    o.k = w / NC;
+    o.m = (w - o.k * NC) * VEC;
+    const I4 dk = *reinterpret_cast<const I4*>(sD + 4 * o.k);
+    o.jx0 = dk.x & 1; o.jy0 = (dk.x >> 1) & 1; o.kc = (dk.x >> 2) & 3;
+    const bool fromg = LF && o.m < A.gin_k;
     const int rk = fromg ? A.gin_k : NFRE;               // frequencies per direction of the source rows
-    const size_t rn = (size_t)NANG * rk;
-    const T* own = src + (size_t)iq[0] * rn;
-    const int el = k * rk + m;
-    b[0] = *reinterpret_cast<const VT*>(own + el);
-    b[1] = *reinterpret_cast<const VT*>(src + (size_t)iq[1 + jx0] * rn + el);
-    b[2] = *reinterpret_cast<const VT*>(src + (size_t)iq[3 + 2 * jy0] * rn + el);
-    b[3] = *reinterpret_cast<const VT*>(src + (size_t)iq[4 + 2 * jy0] * rn + el);
-    b[4] = *reinterpret_cast<const VT*>(src + (size_t)iq[7 + 2 * kc] * rn + el);
-    b[5] = *reinterpret_cast<const VT*>(src + (size_t)iq[8 + 2 * kc] * rn + el);
-    b[6] = *reinterpret_cast<const VT*>(own + dk.y * rk + m);
-    b[7] = *reinterpret_cast<const VT*>(own + dk.z * rk + m);
+    o.src = reinterpret_cast<const char*>(fromg ? A.gin : A.f_in);
+    o.rnb = (unsigned)(NANG * rk * (int)sizeof(T));
+    o.off0 = (unsigned)((o.k * rk + o.m) * (int)sizeof(T));
+    o.off6 = (unsigned)((dk.y * rk + o.m) * (int)sizeof(T));
+    o.off7 = (unsigned)((dk.z * rk + o.m) * (int)sizeof(T));
+    o.srcl = o.src + o.off0;
+    return o;
+  };
+  auto ld = [](const char* p) { return *reinterpret_cast<const VT*>(p); };
+  auto issue = [&](int c, VT (&b)[NB]) {
+    const bool full = c < NFULL * PP;
+    const int r = round_of(c);
+    if (!full || c % PP == 0) R[r] = make_round(r);
+    const Rnd& o = R[r];
+    const int q = full ? c % PP : o.q;
+    const int* iq = sI + q * 16;
+    // the own row: in a full round the same point on every lane -- without fast waves a scalar 64-bit base, the gathers add a 32-bit lane
+    // offset (rows lie beyond 2^32 bytes on large grids: 64-bit row starts throughout)
+    const int row0 = full ? ij0 + (q < n ? q : n - 1) : iq[0];
+    const char* own = o.src + (size_t)(unsigned)row0 * o.rnb;
+    b[0] = ld(own + o.off0);
+    b[1] = ld(o.srcl + (size_t)(unsigned)iq[1 + o.jx0] * o.rnb);      // (one 32 x 32 + 64-bit multiply-add per address)
+    b[2] = ld(o.srcl + (size_t)(unsigned)iq[3 + 2 * o.jy0] * o.rnb);
+    b[3] = ld(o.srcl + (size_t)(unsigned)iq[4 + 2 * o.jy0] * o.rnb);
+    b[4] = ld(o.srcl + (size_t)(unsigned)iq[7 + 2 * o.kc] * o.rnb);
+    b[5] = ld(o.srcl + (size_t)(unsigned)iq[8 + 2 * o.kc] * o.rnb);
+    b[6] = ld(own + o.off6);
+    b[7] = ld(own + o.off7);
     if constexpr (OBS) {
-      const T* o = A.obs + (size_t)iq[0] * 8 * NFRE + m;
-      b[8] = *reinterpret_cast<const VT*>(o + (2 + jx0) * NFRE);      // OBSLON(JXO(K,1))
-      b[9] = *reinterpret_cast<const VT*>(o + jy0 * NFRE);            // OBSLAT(JYO(K,1))
-      b[10] = *reinterpret_cast<const VT*>(o + (4 + kc) * NFRE);      // OBSCOR(KCR(K,1))
+      const T* ob = A.obs + (size_t)row0 * 8 * NFRE + o.m;
+      b[8] = *reinterpret_cast<const VT*>(ob + (2 + o.jx0) * NFRE);      // OBSLON(JXO(K,1))
+      b[9] = *reinterpret_cast<const VT*>(ob + o.jy0 * NFRE);            // OBSLAT(JYO(K,1))
+      b[10] = *reinterpret_cast<const VT*>(ob + (4 + o.kc) * NFRE);      // OBSCOR(KCR(K,1))
     }
   };
+  const bool carry = A.m0 > 0 || A.m1 < NFRE;      // some frequencies are not advected (wave-uniform: the product's step advects all)
+  const T cmtodeg = sK[NANG * 4];
   auto finish = [&](int c, const VT (&b)[NB]) {
-    int q, k, m;
-    chunk_of(c, q, k, m);
+    const Rnd& o = R[round_of(c)];
+    const int q = c < NFULL * PP ? c % PP : o.q, k = o.k, m = o.m;
     T r[VEC];
     if constexpr (MODE == 2) {
 #pragma unroll
       for (int i = 0; i < VEC; i++) r[i] = T(0.3) * b[0][i] + T(0.1) * (((b[1][i] + b[2][i]) + (b[3][i] + b[4][i])) + ((b[5][i] + b[6][i]) + b[7][i]));
     } else {
-      const int sel = sD[4 * k];
-      const int jx0 = sel & 1, jy0 = (sel >> 1) & 1, kc = (sel >> 2) & 3;
+      const int jx0 = o.jx0, jy0 = o.jy0, kc = o.kc;
       const T* pq = sPt + q * PTW;
       const T zd = pq[0], acpm1 = pq[1], ga = pq[2], tanph = pq[3], wl = pq[6 + jy0], omwl = pq[12 + jy0], wc = pq[8 + kc], omwc = pq[14 + kc];
-      const T cmtodeg = sK[NANG * 4];
       const VT kk = *reinterpret_cast<const VT*>(sK + 4 * k);      // (double precision: two 16-byte reads)
       const T kk2 = sizeof(T) == 4 ? kk[2 % VEC] : sK[4 * k + 2], kk3 = sizeof(T) == 4 ? kk[3 % VEC] : sK[4 * k + 3];
 #if ECWAM_HIP_CTU_STRICT
@@ -545,9 +563,11 @@ __device__ __forceinline__ void v4_advect_tile(const V4Adv<T>& A, int ij0, int n
         r[i] = rr.x; r[i + 1] = rr.y;
       }
 #endif
+      if (carry) {
 #pragma unroll
-      for (int i = 0; i < VEC; i++)
-        if (m + i < A.m0 || m + i >= A.m1) r[i] = b[0][i];      // outside the advected range: carried over
+        for (int i = 0; i < VEC; i++)
+          if (m + i < A.m0 || m + i >= A.m1) r[i] = b[0][i];      // outside the advected range: carried over
+      }
     }
     T* d = sT + m * RS + q * NANG + k;
 #pragma unroll
