@@ -23,6 +23,8 @@ OUTBS_SEP_FIELDS = ("mp1", "mp2", "wdw", "shww", "shts", "mdww", "mdts", "mpww",
 OUTBS_PART_FIELDS = OUTBS_SEP_FIELDS + ("swh1", "mwd1", "mwp1", "swh2", "mwd2", "mwp2", "swh3", "mwd3", "mwp3")
 # columns of ecwam_hip_outbs_extremes (include/ecwam_hip.h): OUTBLOCK parameters 29, 30, 31, 33, 34, 57, 70, 71, 72 (KURTOSIS), 78-81 (W_MAXH)
 OUTBS_EXT_FIELDS = ("c4", "bfi", "qp", "hmax", "tmax", "c3", "eta_m", "r", "xnslc", "cmax_f", "hmax_n", "cmax_st", "hmax_st")
+# columns of ecwam_hip_outbs_absolute (include/ecwam_hip.h): OUTBLOCK parameters 1, 2, 3, EM, 6, 20, 21, 22 of the output spectrum FL2ND
+OUTBS_ABS_FIELDS = ("swh", "mwd", "mwp", "em", "pp1d", "mp1", "mp2", "wdw")
 
 
 class EcwamHipError(RuntimeError):
@@ -334,6 +336,23 @@ class HipContext:
              self._real(ff, (ff.shape[0], NFF), "FF")]
         self._chk(self.lib.ecwam_hip_outbs_extremes(self._h, kijs, kijl, *a, 1 if kurtosis_only else 0,
                                                     self._real(out, (out.shape[0], len(OUTBS_EXT_FIELDS)), "OUT"), _stream_ptr()))
+
+    def outbs_absolute(self, kijs, kijl, fl1, wvprpt, ucur, vcur, ff, out, fl2nd=None, zmiss: float = -999.0, flags: int = 0):
+        """The parameters of the output spectrum FL2ND (ecwam_hip_outbs_absolute: INTPOL to the absolute frame when IREFRA = 2 / 3, the ice
+        noise reshaping when LICERUN and not LMASKICE) of rows [kijs, kijl) into out[:, 8], columns OUTBS_ABS_FIELDS.  ucur / vcur: reals
+        [>= kijl], within [-1.5, 1.5] m/s (None when IREFRA is 0 or 1, as wvprpt).  fl2nd: receives FL2ND when given."""
+        nrow = fl1.shape[0]
+        rows = [nrow, out.shape[0]] + [a.shape[0] for a in (wvprpt, ucur, vcur, ff, fl2nd) if a is not None]
+        if not (0 <= kijs <= kijl <= min(rows)):
+            raise ValueError("OUTBS_ABSOLUTE: KIJS/KIJL outside the operands")
+        opt = lambda a, shape, name: None if a is None else self._real(a, shape, name)
+        a = [self._real(fl1, (nrow, self.NANG, self.NFRE), "FL1"),
+             opt(wvprpt, (0 if wvprpt is None else wvprpt.shape[0], NWPR, self.NFRE), "WVPRPT"),
+             opt(ucur, (0 if ucur is None else ucur.shape[0],), "UCUR"), opt(vcur, (0 if vcur is None else vcur.shape[0],), "VCUR"),
+             opt(ff, (0 if ff is None else ff.shape[0], NFF), "FF")]
+        self._chk(self.lib.ecwam_hip_outbs_absolute(self._h, kijs, kijl, *a, int(flags), float(zmiss),
+                                                    self._real(out, (out.shape[0], len(OUTBS_ABS_FIELDS)), "OUT"),
+                                                    opt(fl2nd, (0 if fl2nd is None else fl2nd.shape[0], self.NANG, self.NFRE), "FL2ND"), _stream_ptr()))
 
     def outwnorm(self, field, column: int, n: int, zmiss: float = -999.0):
         """(average, minimum, maximum, count) of field[:n, column] over the values != zmiss."""

@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libecwam_hip.so")
-SOURCES = ["capi.hip", "propag.hip", "implsch4.hip", "implsch4a.hip", "implsch4x.hip", "implsch4r.hip", "implsch4rd.hip", "outbs.hip", "outbs_sep.hip", "outbs_ext.hip", "outbs_part.hip"]
+SOURCES = ["capi.hip", "propag.hip", "implsch4.hip", "implsch4a.hip", "implsch4x.hip", "implsch4r.hip", "implsch4rd.hip", "outbs.hip", "outbs_sep.hip", "outbs_ext.hip", "outbs_part.hip", "outbs_fl2nd.hip"]
 # objects that are a second compilation of another source: object name -> (source, extra flags; a later -O overrides the earlier one).
 # implsch4rd = the double precision RARE builds of k_implsch4 as the two-kernel split (V4R_DP = 2) at -O3: as ONE function they fault on the device
 # at -O3 (implsch4r.hip; round 5 shipped that function at -O2) -- the split passes at every optimisation level and is bit-identical

@@ -29,6 +29,7 @@ struct ecwam_hip_ctx {
   int NANG, NFRE, NFRE_RED;
   void* dtab = nullptr;  // DevTab<T> in device memory
   double* norm_scratch = nullptr;   // ecwam_hip_outwnorm: per-context reduction scratch (4 + 4 x 256 doubles)
+  void* itab = nullptr;  // IntpolTab<T> (csrc/outbs_fl2nd.hip) in device memory when IREFRA = 2 / 3: INTPOL's source-frequency tables
   // fourth kernel generation (implsch_v4.h): DIA rotations K1 = K -+ r1, K2 = K +- r2, NSDSNTH = nh; ok = the tables have that structure
   int v4_ok = 0, v4_r1 = 0, v4_r2 = 0, v4_nh = 0, v4_shelter = 0;
   int implsch_last = 0; // generation the last ecwam_hip_implsch call launched (4; 0 before the first call)
@@ -85,6 +86,9 @@ template <typename T> int launch_outbs_sepwisw(const void*, int, int, const void
 template <typename T> int launch_outbs_partition(const void*, int, int, const void*, const void*, const int*, const void*, const void*, double, void*, int,
                                                   int, hipStream_t);
 template <typename T> int launch_outbs_extremes(const void*, int, int, const void*, const void*, const void*, int, void*, int, int, hipStream_t);
+template <typename T> int launch_outbs_absolute(const void*, const void*, int, int, int, const void*, const void*, const void*, const void*, const void*,
+                                                 double, void*, void*, int, int, hipStream_t);
+size_t intpol_tab_build(const ecwam_hip_params*, const ecwam_hip_tables*, int, std::vector<unsigned char>&);
 template <typename T> void launch_norm(const void*, int, int, double, double*, int, hipStream_t);
 template <typename T> void launch_newwind(const void*, int, void*, const void*, int, hipStream_t);
 template <typename T> void launch_nosource(const void*, int, int, int, void*, void*, int*, hipStream_t);
@@ -470,7 +474,7 @@ int ecwam_hip_create(const ecwam_hip_params* p, const ecwam_hip_tables* t, int r
 #define HIPCHK_CTX(x)                                                                              \
   do {                                                                                             \
     hipError_t e_ = (x);                                                                           \
-    if (e_ != hipSuccess) { if (c->dtab) (void)hipFree(c->dtab); delete c; return fail(std::string(#x) + ": " + hipGetErrorString(e_)); } \
+    if (e_ != hipSuccess) { if (c->dtab) (void)hipFree(c->dtab); if (c->itab) (void)hipFree(c->itab); delete c; return fail(std::string(#x) + ": " + hipGetErrorString(e_)); } \
   } while (0)
   if (real_bytes == 4) {
     std::vector<DevTab<float>> h(1);
@@ -486,6 +490,14 @@ int ecwam_hip_create(const ecwam_hip_params* p, const ecwam_hip_tables* t, int r
     v4_probe<double>(h[0], c);
     HIPCHK_CTX(hipMalloc(&c->dtab, sizeof(DevTab<double>)));
     HIPCHK_CTX(hipMemcpy(c->dtab, h.data(), sizeof(DevTab<double>), hipMemcpyHostToDevice));
+  }
+  if (p->irefra >= 2) {   // INTPOL (ecwam_hip_outbs_absolute): FREQ, DFREQTH, deep-water WAVN and the f**-5 factor of M = 1 .. NFRE_MAX
+    std::vector<unsigned char> h;
+    const size_t nb = intpol_tab_build(p, t, real_bytes, h);
+    if (nb) {               // (NFRE_MAX beyond the table: ecwam_hip_outbs_absolute refuses, everything else is served)
+      HIPCHK_CTX(hipMalloc(&c->itab, nb));
+      HIPCHK_CTX(hipMemcpy(c->itab, h.data(), nb, hipMemcpyHostToDevice));
+    }
   }
 #undef HIPCHK_CTX
   // IMPLSCH runs k_implsch4 (implsch_v4.h) and nothing else since round 5: refuse here what its builds do not cover, with the reason
@@ -510,6 +522,7 @@ int ecwam_hip_destroy(ecwam_hip_ctx* c) {
   if (!c) return 0;
   if (c->dtab) (void)hipFree(c->dtab);
   if (c->norm_scratch) (void)hipFree(c->norm_scratch);
+  if (c->itab) (void)hipFree(c->itab);
   if (c->fin) (void)hipFree(c->fin);
   if (c->wi) (void)hipFree(c->wi);
   if (c->adv_pt) (void)hipFree(c->adv_pt);
@@ -962,6 +975,27 @@ int ecwam_hip_outbs_extremes(ecwam_hip_ctx* c, int kijs, int kijl, const void* f
   DISPATCH(rc = launch_outbs_extremes<float>(c->dtab, kijs, kijl, fl1, wvprpt, ff, flags, out, c->NANG, c->NFRE, s),
            rc = launch_outbs_extremes<double>(c->dtab, kijs, kijl, fl1, wvprpt, ff, flags, out, c->NANG, c->NFRE, s));
   if (rc) return fail("ecwam_hip_outbs_extremes: unsupported spectral size");
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+int ecwam_hip_outbs_absolute(ecwam_hip_ctx* c, int kijs, int kijl, const void* fl1, const void* wvprpt, const void* ucur, const void* vcur,
+                             const void* ff, int flags, double zmiss, void* out, void* fl2nd, void* stream) {
+  if (!c) return fail("null context");
+  if (kijl < kijs || kijs < 0) return fail("ecwam_hip_outbs_absolute: bad range");
+  if (flags) return fail("ecwam_hip_outbs_absolute: unknown flags");
+  const bool intpol = c->p.irefra >= 2, ice = c->p.licerun && !c->p.lmaskice;
+  if (kijl > kijs && (!fl1 || !out)) return fail("ecwam_hip_outbs_absolute: null pointer");
+  if (kijl > kijs && intpol && (!wvprpt || !ucur || !vcur)) return fail("ecwam_hip_outbs_absolute: IREFRA = 2 / 3 needs wvprpt, ucur and vcur");
+  if (kijl > kijs && ice && !ff) return fail("ecwam_hip_outbs_absolute: LICERUN without LMASKICE needs ff (CICOVER, WSWAVE)");
+  if (fl2nd && fl2nd == fl1) return fail("ecwam_hip_outbs_absolute: FL1 and FL2ND must not alias");
+  if (intpol && !c->itab) return fail("ecwam_hip_outbs_absolute: NFRE_MAX of INTPOL exceeds the library's table");
+  hipStream_t s = (hipStream_t)stream;
+  const int mode = (intpol ? 1 : 0) | (ice ? 2 : 0);
+  int rc;
+  DISPATCH(rc = launch_outbs_absolute<float>(c->dtab, c->itab, kijs, kijl, mode, fl1, wvprpt, ucur, vcur, ff, zmiss, out, fl2nd, c->NANG, c->NFRE, s),
+           rc = launch_outbs_absolute<double>(c->dtab, c->itab, kijs, kijl, mode, fl1, wvprpt, ucur, vcur, ff, zmiss, out, fl2nd, c->NANG, c->NFRE, s));
+  if (rc) return fail("ecwam_hip_outbs_absolute: unsupported spectral size");
   HIPCHK(hipGetLastError());
   return 0;
 }

@@ -2,10 +2,9 @@
 // with -- significant wave height, mean direction, mean period, peak period (outblock.F90:204,223-263 with FEMEAN
 // femean.F90:84-121, STHQ sthq.F90:75-120 and DOMINANT_PERIOD dominant_period.F90:76-112) -- and the OUTWNORM statistics (average / minimum / maximum / non-missing count, outwnorm.F90), so
 // that a device-resident run can be checked without copying the spectra back.
-#include "dev.h"
+#include "outbs_point.h"
 
-// One wavefront per point.  The spectrum goes through an LDS tile [M][NANG|1]: lane = M sums MAX(F,EPSMIN) over K in the
-// reference's order (FEMEAN), lane = K sums F*DFIM over M in the reference's order (STHQ).
+// One wavefront per point.  The spectrum goes through an LDS tile [M][NANG|1]; the sums over it are outbs_point (csrc/outbs_point.h).
 template <typename T>
 __global__ void __launch_bounds__(256) k_outbs(const DevTab<T>* __restrict__ tp, int kijs, int kijl, const T* __restrict__ fl1,
                                                T zmiss, T* __restrict__ out) {
@@ -23,56 +22,7 @@ __global__ void __launch_bounds__(256) k_outbs(const DevTab<T>* __restrict__ tp,
   }
   __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
   __builtin_amdgcn_wave_barrier();
-  const bool actm = lane < NFRE, actk = lane < NANG;
-  // FEMEAN
-  T t2 = T(0);
-  if (actm) {
-    const T* p = sF + lane * NAP;
-    t2 = m_max(p[0], tb.EPSMIN);
-    for (int kk = 1; kk < NANG; kk++) t2 = t2 + m_max(p[kk], tb.EPSMIN);
-  }
-  T EM, FM;
-  usum2(actm ? t2 * tb.DFIM[lane] : T(0), actm ? tb.DFIMOFR[lane] * t2 : T(0), EM, FM);
-  const T tl = lane_get(t2, NFRE - 1);
-  EM = EM + tb.WETAIL * tb.FR[NFRE - 1] * tb.DELTH * tl;
-  FM = FM + tb.FRTAIL * tb.DELTH * tl;
-  FM = EM / FM;
-  FM = m_max(FM, tb.FR[0]);
-  // STHQ
-  T temp = T(0);
-  if (actk)
-    for (int m = 0; m < NFRE; m++) temp = temp + sF[m * NAP + lane] * tb.DFIM[m];
-  T SI, CI;
-  usum2(actk ? tb.SINTH[lane] * temp : T(0), actk ? tb.COSTH[lane] * temp : T(0), SI, CI);
-  if (CI == T(0)) CI = tb.EPSMIN;
-  T THQ = m_atan2(SI, CI);
-  if (THQ < T(0)) THQ = THQ + tb.ZPI;
-  // DOMINANT_PERIOD: lane = K finds its maximum, lane = M sums the cropped directions in the reference's order
-  T fmx = T(0);
-  if (actk)
-    for (int m = 0; m < NFRE; m++) fmx = m_max(fmx, sF[m * NAP + lane]);
-  const T FCROP = T(0.1) * umax(actk ? fmx : T(0));
-  T f1d = T(0);
-  if (actm) {
-    const T* p = sF + lane * NAP;
-    for (int kk = 0; kk < NANG; kk++)
-      if (p[kk] > FCROP) f1d = f1d + p[kk] * tb.DELTH;
-    f1d = (f1d * f1d) * (f1d * f1d);
-  }
-  T EM4, DP;
-  usum2(actm ? tb.DFIM[lane] * f1d : T(0), actm ? tb.DFIMFR[lane] * f1d : T(0), EM4, DP);
-  DP = (EM4 > T(0) && DP > tb.EPSMIN) ? EM4 / DP : T(0);
-  if (lane == 0) {
-    T* o = out + (size_t)ij * 5;
-    const T DEG = T(180.0) / tb.PI;
-    o[0] = T(4) * m_sqrt(m_max(EM, T(0)));
-    T d = DEG * THQ + T(180.0);
-    d = d - T(360.0) * T((int)(d / T(360.0)));  // MOD(.,360) for d >= 0
-    o[1] = d;
-    o[2] = (FM > T(0)) ? T(1) / FM : zmiss;
-    o[3] = EM;
-    o[4] = (DP > T(0)) ? DP : zmiss;
-  }
+  outbs_point(tb, sF, lane, zmiss, out + (size_t)ij * 5);
 }
 
 // OUTWNORM: partial sums in double (the reference accumulates WNORM in JWRU), two deterministic stages

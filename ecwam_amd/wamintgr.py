@@ -19,6 +19,7 @@ from .tables import Config, Tables
 OUTBS_SEP_FIELDS = api.OUTBS_SEP_FIELDS     # the columns of Wamintgr.outbs_sepwisw()
 OUTBS_EXT_FIELDS = api.OUTBS_EXT_FIELDS     # the columns of Wamintgr.outbs_extremes()
 OUTBS_PART_FIELDS = api.OUTBS_PART_FIELDS   # the columns of Wamintgr.outbs_partition()
+OUTBS_ABS_FIELDS = api.OUTBS_ABS_FIELDS     # the columns of Wamintgr.outbs_absolute()
 
 
 class HaloExchange:
@@ -601,6 +602,15 @@ class Wamintgr:
         out = torch.zeros((self.n, len(api.OUTBS_EXT_FIELDS)), dtype=self.dtype, device=self.dev)
         self.ctx.outbs_extremes(0, self.n, self.fl1, self.wvprpt, self.ff, out, kurtosis_only=kurtosis_only)
         return out
+
+    # ---- the parameters of OUTBLOCK's output spectrum FL2ND on the device: [n][8], columns api.OUTBS_ABS_FIELDS.  With IREFRA = 2 / 3 the
+    # spectrum is first taken to the absolute frame with the model's currents (INTPOL); store_spectrum: also returns FL2ND [n][NANG][NFRE]
+    def outbs_absolute(self, store_spectrum: bool = False):
+        out = torch.zeros((self.n, len(api.OUTBS_ABS_FIELDS)), dtype=self.dtype, device=self.dev)
+        fl2nd = torch.empty((self.n, self.cfg.nang, self.cfg.nfre), dtype=self.dtype, device=self.dev) if store_spectrum else None
+        u, v = (self.u_ext, self.v_ext) if self.irefra >= 2 else (None, None)
+        self.ctx.outbs_absolute(0, self.n, self.fl1, self.wvprpt, u, v, self.ff, out, fl2nd=fl2nd)
+        return (out, fl2nd) if store_spectrum else out
 
     def swh_norm(self):
         return self.ctx.outwnorm(self.outbs(), 0, self.n)

@@ -328,6 +328,8 @@ int ecwam_hip_propags2_implsch(ecwam_hip_ctx *ctx, const void *f1, void *f3, int
  * degrees / meteorological convention (STHQ), mean period 1/FM or zmiss, EM, peak period pp1d (DOMINANT_PERIOD) or zmiss.
  * ecwam_hip_outwnorm: the OUTWNORM statistics of one such field: result[4] (HOST doubles) = average, minimum, maximum over the
  * n values field[i*stride] that differ from zmiss, and their count (outwnorm.F90).  Synchronises the stream.
+ * These are the parameters of fl1 as passed (FL2ND = FL1); those of the absolute-frame output spectrum (IREFRA = 2 / 3, ice noise
+ * reshaping): ecwam_hip_outbs_absolute.
  */
 int ecwam_hip_outbs(ecwam_hip_ctx *ctx, int kijs, int kijl, const void *fl1, double zmiss, void *out, void *stream);
 int ecwam_hip_outwnorm(ecwam_hip_ctx *ctx, const void *field, int stride, int n, double zmiss, double *result, void *stream);
@@ -348,6 +350,7 @@ int ecwam_hip_outwnorm(ecwam_hip_ctx *ctx, const void *field, int stride, int n,
  *    9 P1SEA [23]  10 P1SWELL [24]  11 P2SEA [25]  12 P2SWELL [26]  13 SPRDSEA [27]  14 SPRDSWELL [28]
  * flags: bit 0 -- CLDOMAIN = 's' (a small domain): the first mask only, without the R test, the second mask and the walk over
  * frequencies (sepwisw.F90:177).  OUTWNORM statistics of a column: ecwam_hip_outwnorm(out + column, stride = 15).
+ * Columns 0-2 from the absolute-frame output spectrum (IREFRA = 2 / 3, ice noise reshaping): ecwam_hip_outbs_absolute.
  */
 int ecwam_hip_outbs_sepwisw(ecwam_hip_ctx *ctx, int kijs, int kijl, const void *fl1, const void *xllws, const void *wvprpt, const void *ff,
                             int flags, double zmiss, void *out, void *stream);
@@ -364,6 +367,7 @@ int ecwam_hip_outbs_sepwisw(ecwam_hip_ctx *ctx, int kijs, int kijl, const void *
  * A point has at most NPMAX = 20 peaks (in order of discovery, M-major) and at most 25 sweeps per peak.  flags: 0 only; bit 0 (CLDOMAIN =
  * 's') is refused -- the reference hands SEP3TR an FSEA it has not computed in that branch -- and so is every other bit.  The spectral
  * sizes of ecwam_hip_outbs_sepwisw.  OUTWNORM statistics of a column: ecwam_hip_outwnorm(out + column, stride = 24).
+ * Columns 0-2 from the absolute-frame output spectrum (IREFRA = 2 / 3, ice noise reshaping): ecwam_hip_outbs_absolute.
  */
 int ecwam_hip_outbs_partition(ecwam_hip_ctx *ctx, int kijs, int kijl, const void *fl1, const void *xllws, const int *mij, const void *wvprpt,
                               const void *ff, int flags, double zmiss, void *out, void *stream);
@@ -382,9 +386,34 @@ int ecwam_hip_outbs_partition(ecwam_hip_ctx *ctx, int kijs, int kijl, const void
  * 78-81 is requested).  Other bits: error.  AKI's open iteration is bounded at 100 Newton steps.  Not served: the FL2ND transforms
  * (INTPOL, LSECONDORDER; KURTOSIS and W_MAXH read FL1), OUTSETWMASK, SIG_TH / EPS / XNU and PHIST (not OUTBLOCK parameters).
  * OUTWNORM statistics of a column: ecwam_hip_outwnorm(out + column, stride = 13).
+ * The INTPOL transform and the ice noise reshaping of FL2ND, for the parameters that read FL2ND: ecwam_hip_outbs_absolute.
  */
 int ecwam_hip_outbs_extremes(ecwam_hip_ctx *ctx, int kijs, int kijl, const void *fl1, const void *wvprpt, const void *ff, int flags,
                              void *out, void *stream);
+
+/*
+ * The output spectrum FL2ND of OUTBLOCK and the parameters that read it (outblock.F90:159-263, 350-359; LSECONDORDER = F) for rows
+ * [kijs,kijl).  FL2ND is built per point on the chip, as params.irefra / licerun / lmaskice of ecwam_hip_create select:
+ *   IREFRA = 2 / 3: INTPOL(FL1 -> FL2ND, WAVNUM, UCUR, VCUR, IRA = 1) (intpol.F90:98-271), the spectrum in the absolute frame: every bin
+ *     moves to FREQ + K.U/ZPI, the f**-5 tail up to FR(NFRE) + ZPI/G FR(NFRE)**2 CURRENT_MAX is folded back in, energy of negative
+ *     shifted frequency goes to the opposite direction, a point with no bin above EPSMIN gives EPSMIN everywhere; IREFRA = 0 / 1: FL2ND = FL1;
+ *   LICERUN and not LMASKICE: then the noise level under sea ice is reshaped (outblock.F90:175-194) with CICOVER = ff[ij][2] and
+ *     WSWAVE = ff[ij][3].
+ * Inputs: fl1; WAVNUM = wvprpt[ij][0][:] and ucur / vcur, device reals [>= kijl] (UCUR, VCUR of the point; all three may be NULL when
+ * IREFRA is 0 or 1); ff (may be NULL unless the ice reshaping is on).  CURRENT_MAX = 1.5 m/s (yowcurr.F90:18) is a constant of the library:
+ * the reference clips the components of the current to [-CURRENT_MAX, CURRENT_MAX] when it reads them (wamcur.F90:82-84) and sizes the tail
+ * extension with it; components outside that range are the caller's error and are not clipped here.
+ * out[npts][8] indexed by the absolute row ij (columns; OUTBLOCK parameter numbers in brackets):
+ *    0 swh  4*SQRT(EM) of FEMEAN [1]    1 mwd  mean direction of STHQ, degrees [2]    2 mwp  mean period 1/FM or zmiss [3]    3 EM
+ *    4 pp1d peak period of DOMINANT_PERIOD or zmiss [6]    5 mp1  MWP1 [20]    6 mp2  MWP2 [21]    7 wdw  WDIRSPREAD, LLPEAKF = F [22]
+ * Columns 0-4 are bit for bit what ecwam_hip_outbs gives on FL2ND, columns 5-7 what ecwam_hip_outbs_sepwisw gives in its columns 0-2.
+ * fl2nd (may be NULL): device FL2ND[npts][NANG][NFRE] that receives the rows [kijs,kijl) of the output spectrum (for SE10MEAN / SEBTMEAN,
+ * spectral output or the host); with NULL nothing but out is written.  fl2nd must not overlap fl1 (fl2nd == fl1 is refused).  The scatter of INTPOL uses no atomics: results do not depend on
+ * scheduling.  flags: 0 only.  The spectral sizes of ecwam_hip_outbs_sepwisw.  Not served: CAL_SECOND_ORDER_SPEC (LSECONDORDER),
+ * OUTSETWMASK, IRA = -1.  OUTWNORM statistics of a column: ecwam_hip_outwnorm(out + column, stride = 8).
+ */
+int ecwam_hip_outbs_absolute(ecwam_hip_ctx *ctx, int kijs, int kijl, const void *fl1, const void *wvprpt, const void *ucur, const void *vcur,
+                             const void *ff, int flags, double zmiss, void *out, void *fl2nd, void *stream);
 
 /* NEWWIND forcing hand-over (newwind.F90:126-161): FF <- FF_NEXT members + TAUW cap.  ecwam_hip_newwind takes ICODE_WND = ICODE
  * of the parameters; a coupled host (LWCOU) passes ICODE_CPL through ecwam_hip_newwind_icode (newwind.F90:120-124). */
