@@ -14,9 +14,8 @@ LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libecwam_hip.so")
 SOURCES = ["capi.hip", "propag.hip", "implsch4.hip", "implsch4a.hip", "implsch4x.hip", "implsch4r.hip", "implsch4rd.hip", "outbs.hip", "outbs_sep.hip", "outbs_ext.hip", "outbs_part.hip", "outbs_fl2nd.hip"]
 # objects that are a second compilation of another source: object name -> (source, extra flags; a later -O overrides the earlier one).
-# implsch4rd = the double precision RARE builds of k_implsch4 as the two-kernel split (V4R_DP = 2) at -O3: as ONE function they fault on the device
-# at -O3 (implsch4r.hip; round 5 shipped that function at -O2) -- the split passes at every optimisation level and is bit-identical
-DERIVED = {"implsch4r.hip": ("implsch4r.hip", ["-DV4R_PREC=1"]), "implsch4rd.hip": ("implsch4r.hip", ["-DV4R_PREC=2", "-DV4R_DP=2"])}
+# implsch4r / implsch4rd = the single / double precision RARE builds of k_implsch4 (double precision: the two-kernel split, implsch4r.hip)
+DERIVED = {"implsch4r.hip": ("implsch4r.hip", ["-DV4R_PREC=1"]), "implsch4rd.hip": ("implsch4r.hip", ["-DV4R_PREC=2"])}
 HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 # IMPLSCH is VALU-issue bound: single-precision divide/sqrt by the hardware reciprocal / square root plus one
 # refinement (<= 2.5 ulp) instead of the correctly rounded sequences; double precision is unaffected.
@@ -36,21 +35,11 @@ IMPLSCH_SOURCES = ("implsch4.hip", "implsch4a.hip", "implsch4x.hip", "implsch4r.
 #   "strict3"  both
 #   "strict7"  both + floating-point contraction off (no FMA the source does not spell out)
 # A variant is written to libecwam_hip_<variant>.so next to the product library; ECWAM_HIP_LIB=<path> makes lib.load() use it.
+# (The index assertions of implsch_v4.h::V4_CHK are no variant: a developer adds the plain -DV4_CHECK=1 to the flags of the build at hand.)
 VARIANTS = {"": FAST_DIV, "exactdiv": ["-DECWAM_HIP_STRICT=0"], "strict1": ["-DECWAM_HIP_STRICT=1"], "strict2": FAST_DIV + ["-DECWAM_HIP_STRICT=2"],
             "site4": ["-DECWAM_HIP_STRICT=4"], "site8": ["-DECWAM_HIP_STRICT=8"], "site32": ["-DECWAM_HIP_STRICT=32"],
             "strict3": ["-DECWAM_HIP_STRICT=3"], "strict7": ["-DECWAM_HIP_STRICT=3", "-ffp-contract=off"],
             "noieee": FAST_DIV + ["-mno-amdgpu-ieee", "-fno-honor-nans"],
-            # the double precision RARE builds of k_implsch4 (profiles/r05_rare_dp_rootcause.txt, r06_rare_dp_note.txt): the object implsch4rd
-            # (product: the two-kernel split at -O3, V4R_DP = 2) as the one kernel at -O3 (faults), at -O3 with index assertions, at -O2
-            "rdp": FAST_DIV + ["-O3", "-DV4R_DP=1"], "rdpchk": FAST_DIV + ["-O3", "-DV4R_DP=1", "-DV4_CHECK=1"], "rdpO2": FAST_DIV + ["-O2", "-DV4R_DP=1"],
-            # every build of k_implsch4 as the two-kernel split (PART 1: through the second SINFLX call | PART 2: sweep, fluxes, tail, stores)
-            "split": FAST_DIV + ["-DV4_SPLIT_ALL=1", "-DV4R_DP=2"],
-            # A/B partners of the mechanisms of round 5 that are in the product (profiles/r05_scalar_prefetch.txt): the per-interaction / per-row
-            # coefficient records fetched ahead (V4_RECPF, single precision) off; the double precision sweep's record as the compiler places its
-            # loads (V4_RECV = 0); the all-reduces of a SINPUT row one after the other instead of in one batch (V4_REDN = 0)
-            "norecpf": FAST_DIV + ["-DV4_RECPF=0"], "norecs": FAST_DIV + ["-DV4_RECV=0"], "noredn": FAST_DIV + ["-DV4_REDN=0"],
-            # round 6: the library with the go / no-go probe of the one-kernel step (implsch4a.hip, flags bit 1 of ecwam_hip_propags2_implsch)
-            "advprobe": FAST_DIV + ["-DV4_ADV_PROBE=1"],
             # the on-the-fly CTU weights (k_propags2_otf and the advecting load of k_implsch4) in ctuw.F90's order of operations, contraction off:
             # bit-identical to the stored-weight scheme (csrc/ctu.h; the product hoists the factors and fuses the multiply-adds)
             "ctustrict": FAST_DIV,
@@ -60,9 +49,7 @@ VARIANTS = {"": FAST_DIV, "exactdiv": ["-DECWAM_HIP_STRICT=0"], "strict1": ["-DE
 # flags a variant adds to EVERY source it rebuilds (not only the IMPLSCH units)
 VARIANT_ANY = {"ctustrict": ["-DECWAM_HIP_CTU_STRICT=1"]}
 # variants that rebuild only some of the translation units (the other objects are the product's)
-VARIANT_SOURCES = {"ctustrict": ("propag.hip", "implsch4a.hip"), "advprobe": ("implsch4a.hip",), "advO1": ("implsch4a.hip",), "rdp": ("implsch4rd.hip",), "rdpchk": ("implsch4rd.hip",), "rdpO2": ("implsch4rd.hip",),
-                   "split": ("implsch4.hip", "implsch4x.hip", "implsch4r.hip", "implsch4rd.hip"), "norecpf": ("implsch4.hip",), "norecs": ("implsch4.hip",),
-                   "noredn": ("implsch4.hip",)}
+VARIANT_SOURCES = {"ctustrict": ("propag.hip", "implsch4a.hip"), "advO1": ("implsch4a.hip",)}
 
 INCLUDE = os.path.join(HERE, "..", "include", "ecwam_hip.h")
 

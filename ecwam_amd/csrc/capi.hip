@@ -36,7 +36,7 @@ struct ecwam_hip_ctx {
   void* fin = nullptr;  // rows of scalars k_implsch4 hands to its finishing kernel, indexed by the point number; grown on demand
   size_t fin_bytes = 0;
   void* wi = nullptr;   // rows [ij][M][K] for the wind-input coefficient between the two kernels of the split k_implsch4 (only allocated
-  size_t wi_bytes = 0;  // where the split runs: the double precision RARE builds, the "split" build variant of the library)
+  size_t wi_bytes = 0;  // where the split runs: the double precision RARE builds)
   // advection halo exchange (MPEXCHNG): peers, the owned rows each of them needs (concatenated in peer order) and where their rows
   // land; RCCL communicator + a stream of its own so that the exchange runs beside the interior stencil
   int rank = 0, nranks = 1;
@@ -104,8 +104,6 @@ template <typename T> void launch_ctu_prep(const void*, int, int, int, double, d
 template <typename T> int launch_implsch4_adv(const void*, int, int, void*, const void*, void*, void*, int*, void*, void*, double*, const Implsch4AdvArgs*, int, int, int, int, int, int, hipStream_t);
 int implsch4_adv_forms(int, int);
 int implsch4_fin_row();
-int implsch4_split_all();
-int implsch4r_dp_split();
 
 // Does the fourth kernel generation cover these tables?  It needs the pull-form DIA structure with K1W = K -+ r1, K11W = K1W -+ 1,
 // K2W = K +- r2, K21W = K2W +- 1 (kh = 1 / 2) and saturation weights that depend on the tap only (init_sdiss_ardh.F90:88-94: they
@@ -824,6 +822,7 @@ int ecwam_hip_propags2_implsch(ecwam_hip_ctx* c, const void* f1, void* f3, int n
                                int nd3e, const void* wvprpt, void* ff, void* intf, int* mij, void* xllws, double* wam2nemo, double delpro_lf,
                                int ifrelfmax, const void* gin, int gin_nfre, int flags, void* stream) {
   if (!c) return fail("null context");
+  if (flags) return fail("ecwam_hip_propags2_implsch: unknown flags");
   if (!fused_ok(c) || !implsch4_adv_forms(c->NANG, c->real_bytes)) return fail("ecwam_hip_propags2_implsch: no one-kernel build covers the configuration (ecwam_hip_propags2_implsch_supported): call ecwam_hip_propags2_otf and ecwam_hip_implsch");
   if (kijl < kijs || kijs < 0 || kijl > n || nd3s < 1 || nd3e > c->NFRE_RED || nd3e < nd3s - 1) return fail("ecwam_hip_propags2_implsch: bad range");
   if (kijl > kijs && (!f1 || !f3 || !kxlt || !zdello || !cosph || !sinph || !klon || !klat || !kcor || !wlat || !wcor || !cgroup_ext || !cosphm1_ext ||
@@ -855,10 +854,6 @@ int ecwam_hip_propags2_implsch(ecwam_hip_ctx* c, const void* f1, void* f3, int n
   a.gin = gin; a.delpro_lf = dlf; a.gin_k = gin ? gin_nfre : 0; a.mlf = gin ? ifrelfmax : 0;
   a.obs = c->obs;      // ecwam_hip_set_obstructions (LSUBGRID)
   a.gfast = c->fast_g; a.gfast_k = c->fast_g ? c->fast_gk : 0;      // ecwam_hip_set_fastwave_copy, as for ecwam_hip_implsch
-  // flags bit 0: the workgroups in the XCD-aware order of k_propags2_otf (diagnostics: 1 % slower here); bits 8..19: G > 1 = groups of G
-  // consecutive waves per XCD (diagnostics)
-  a.xcd_walk = (flags & 1) ? 1 : (((flags >> 8) & 0xFFF) > 1 ? ((flags >> 8) & 0xFFF) : 0);
-  a.mode = (flags & 2) ? 2 : 1;          // flags bit 1: the go / no-go probe (libraries built with -DV4_ADV_PROBE only)
   const int ext = (c->p.llnormagam || c->p.llgcbz0) ? 1 : 0;
   int rc = -1;
   DISPATCH(rc = launch_implsch4_adv<float>(c->dtab, kijs, kijl, f3, wvprpt, ff, intf, mij, xllws, c->fin, wam2nemo, &a, c->NANG, c->NFRE, c->v4_r1, c->v4_r2, c->v4_nh, ext, s),
@@ -894,10 +889,10 @@ static int implsch_reserve_on(ecwam_hip_ctx* c, int npts, hipStream_t s, bool sy
     (void)sync;
     c->fin_bytes = need;
   }
-  // the split kernel pair parks the wind-input coefficient of every bin between its two halves: the whole library built as the split (build
-  // variant), or a double precision context whose configuration runs the RARE builds (implsch4r.hip: their dp form is the split) -- NOT
-  // every double precision context: the rows are a fourth spectrum-sized array (68 GB at O1280)
-  const bool split = implsch4_split_all() || (c->real_bytes == 8 && implsch4r_dp_split() && runs_rare_builds(c));
+  // the split kernel pair parks the wind-input coefficient of every bin between its two halves: a double precision context whose
+  // configuration runs the RARE builds (implsch4r.hip: their dp form is the split) -- NOT every double precision context: the rows are a
+  // fourth spectrum-sized array (68 GB at O1280)
+  const bool split = c->real_bytes == 8 && runs_rare_builds(c);
   const size_t need_wi = split ? (size_t)(npts > 0 ? npts : 0) * c->NANG * c->NFRE * c->real_bytes : 0;
   if (need_wi > c->wi_bytes) {
     if (c->wi) HIPCHK(hipFree(c->wi));

@@ -16,7 +16,7 @@ int launch_implsch4(const void* tab, int kijs, int kijl, void* fl1, const void* 
   if (NANG == 48 && r1 == 1 && r2 == 4 && nh == 11)      // two points per wavefront, 24 lanes each
     return ext ? launch4<T, 48, 2, 1, 4, 11, true>(V4_ARGS) : launch4<T, 48, 2, 1, 4, 11, false>(V4_ARGS);
   if (NANG == 36 && r1 == 1 && r2 == 3 && nh == 8)
-    return ext ? launch4<T, 36, SP ? 3 : V4_DP36_PP, 1, 3, 8, true>(V4_ARGS) : launch4<T, 36, SP ? 3 : V4_DP36_PP, 1, 3, 8, false>(V4_ARGS);
+    return ext ? launch4<T, 36, 3, 1, 3, 8, true>(V4_ARGS) : launch4<T, 36, 3, 1, 3, 8, false>(V4_ARGS);
   if (NANG == 24 && r1 == 0 && r2 == 2 && nh == 5)
     return ext ? launch4<T, 24, SP ? 5 : 4, 0, 2, 5, true>(V4_ARGS) : launch4<T, 24, SP ? 5 : 4, 0, 2, 5, false>(V4_ARGS);
   if (NANG == 12 && r1 == 0 && r2 == 1 && nh == 3)
@@ -26,7 +26,5 @@ int launch_implsch4(const void* tab, int kijs, int kijl, void* fl1, const void* 
 }
 // elements of the working precision per sea point the caller provides in fin (indexed by the absolute point number, like FL1)
 int implsch4_fin_row() { return V4_NFIN; }
-// 1 when every build of the library runs as the two-kernel split (build variant "split"): the context then owns wind-input rows
-int implsch4_split_all() { return V4_SPLIT_ALL != 0 ? 1 : 0; }
 template int launch_implsch4<float>(const void*, int, int, void*, const void*, void*, void*, int*, void*, void*, double*, void*, int, void*, int, int, int, int, int, int, hipStream_t);
 template int launch_implsch4<double>(const void*, int, int, void*, const void*, void*, void*, int*, void*, void*, double*, void*, int, void*, int, int, int, int, int, int, hipStream_t);

@@ -7,10 +7,6 @@
 #include "implsch_v4_launch.h"
 #include "implsch_adv_args.h"
 
-#ifndef V4_ADV_PROBE
-#define V4_ADV_PROBE 0
-#endif
-
 // returns 0 when launched, -1 when no ADV build covers the configuration (the caller then runs the two kernels)
 template <typename T>
 int launch_implsch4_adv(const void* tab, int kijs, int kijl, void* fl_out, const void* wvprpt, void* ff, void* intf, int* mij, void* xllws, void* fin,
@@ -20,13 +16,11 @@ int launch_implsch4_adv(const void* tab, int kijs, int kijl, void* fl_out, const
   V4Adv<T> adv;
   adv.f_in = (const T*)a->f_in; adv.klon = a->klon; adv.klat = a->klat; adv.kcor = a->kcor; adv.cg = (const T*)a->cg; adv.pt = (const T*)a->pt;
   adv.dirT = (const T*)a->dirT; adv.dirI = a->dirI; adv.xdella = (T)a->xdella; adv.delpro = (T)a->delpro; adv.m0 = a->m0; adv.m1 = a->m1;
-  adv.xcd_walk = a->xcd_walk;
   adv.gin = (const T*)a->gin; adv.delpro_lf = (T)a->delpro_lf; adv.gin_k = a->gin_k; adv.mlf = a->mlf; adv.obs = (const T*)a->obs;
 #define V4_ARGS tab, kijs, kijl, fl_out, wvprpt, ff, intf, mij, xllws, fin, w2n, a->gfast, a->gfast_k, adv, s
   // one direction count: the plain step (ADV 1), with fast waves (3), with obstructions (5), with both (7); each for flag sets A and B (EXT)
 #define V4_ADV_CASE(NA, PPV, R1V, R2V, NHV, LFOK)                                                                                         \
   if (NANG == NA && r1 == R1V && r2 == R2V && nh == NHV) {                                                                              \
-    if (a->mode != 1) return -1;                                                                                                        \
     const int form = (a->gin ? 2 : 0) | (a->obs ? 4 : 0);                                                                               \
     if (!a->gin && a->mlf != 0) return -1;                                                                                              \
     if (form == 0) return ext ? launch4_adv<T, NA, PPV, R1V, R2V, NHV, true, 1>(V4_ARGS) : launch4_adv<T, NA, PPV, R1V, R2V, NHV, false, 1>(V4_ARGS); \
@@ -40,11 +34,7 @@ int launch_implsch4_adv(const void* tab, int kijs, int kijl, void* fl_out, const
     return -1;                                                                                                                          \
   }
   constexpr bool SP = sizeof(T) == 4;
-#if V4_ADV_PROBE
-  if constexpr (SP)
-    if (NANG == 36 && r1 == 1 && r2 == 3 && nh == 8 && a->mode == 2) return ext ? -1 : launch4_adv<T, 36, 3, 1, 3, 8, false, 2>(V4_ARGS);
-#endif
-  V4_ADV_CASE(36, (SP ? 3 : V4_DP36_PP), 1, 3, 8, true)
+  V4_ADV_CASE(36, 3, 1, 3, 8, true)
   // The other direction counts in single precision only.  Their double precision builds were built and measured in round 6 and are NOT
   // shipped: at -O3 the 12-direction builds and the fast-wave builds at 24 directions give wrong numbers (34 000 .. 58 000 of the bins of a
   // 1 109-point grid differ from the two kernels, errors of order one from frequency 7 on), at -O1 the same source is bit-identical to the

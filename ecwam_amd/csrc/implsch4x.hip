@@ -15,8 +15,8 @@ int launch_implsch4x(const void* tab, int kijs, int kijl, void* fl1, const void*
   if (NANG == 48 && r1 == 1 && r2 == 4 && nh == 11)
     return variant == 1 ? launch4<T, 48, 2, 1, 4, 11, false, true, false>(V4_ARGS) : launch4<T, 48, 2, 1, 4, 11, false, false, true>(V4_ARGS);
   if (NANG == 36 && r1 == 1 && r2 == 3 && nh == 8)
-    return variant == 1 ? launch4<T, 36, SP ? 3 : V4_DP36_PP, 1, 3, 8, false, true, false>(V4_ARGS)
-                        : launch4<T, 36, SP ? 3 : V4_DP36_PP, 1, 3, 8, false, false, true>(V4_ARGS);
+    return variant == 1 ? launch4<T, 36, 3, 1, 3, 8, false, true, false>(V4_ARGS)
+                        : launch4<T, 36, 3, 1, 3, 8, false, false, true>(V4_ARGS);
   if (NANG == 24 && r1 == 0 && r2 == 2 && nh == 5)
     return variant == 1 ? launch4<T, 24, SP ? 5 : 4, 0, 2, 5, false, true, false>(V4_ARGS) : launch4<T, 24, SP ? 5 : 4, 0, 2, 5, false, false, true>(V4_ARGS);
   if (NANG == 12 && r1 == 0 && r2 == 1 && nh == 3)

@@ -16,6 +16,4 @@ struct Implsch4AdvArgs {
   void* gfast;                          // compact rows that also receive the first gfast_k frequencies of the new spectrum (or NULL)
   int gfast_k;
   int m0, m1;                           // advected frequencies [m0, m1)
-  int xcd_walk;
-  int mode;                             // 1 = the product; 2 = the go / no-go probe (made-up weights; builds with -DV4_ADV_PROBE only)
 };

@@ -35,7 +35,7 @@
 #else
 #define V4_PHASE_EXIT(k) do { } while (0)
 #endif
-// index checks of the debugging build (-DV4_CHECK=1, build variant "rdpchk"): device-side assert = message + trap
+// index checks of a debugging build (-DV4_CHECK=1): device-side assert = message + trap
 #if defined(V4_CHECK) && V4_CHECK
 #include <cassert>
 #define V4_CHK(c) assert(c)
@@ -157,7 +157,7 @@ __device__ __forceinline__ T v4_allsum1(T v, const V4Rot<T>& r) {
   }
 }
 
-// N independent all-reduces at once (V4_REDN): the exchanges of every stage are issued together and waited for together -- N quantities
+// N independent all-reduces at once: the exchanges of every stage are issued together and waited for together -- N quantities
 // cost the LDS round trips of one.  The first NB come back on every lane of the point; the others (G = 18) are complete on the sixteen
 // lanes of the point's DPP row only, which is what v4_row_total_to_lds needs.  Per quantity the operations and their order are those of
 // v4_allsum / v4_allsum1 / v4_row_total_to_lds: the same bits.
@@ -205,9 +205,6 @@ __device__ __forceinline__ void v4_allsum_n(T (&v)[N], const V4Rot<T>& r) {
     for (int i = 0; i < N; i++) v[i] = v[i] + (e[i] + f[i]);
   }
 }
-#ifndef V4_REDN
-#define V4_REDN 1
-#endif
 
 // maximum over the lanes of a point (the RARE build's PEAK_ANG)
 template <int G, typename T>
@@ -262,22 +259,16 @@ __device__ __forceinline__ V2<T> v4_at(const T* row, const int (&sh)[2 * NSH + 1
 // such window of ONE staged row instead of an odd rotation (two 4-byte reads, two-way bank conflicts by construction) plus an even one of
 // two rows: 28 % fewer LDS instructions in the sweep, which profiles/r05_bench_O320_sp_split_pmc.json shows to be bound by the LDS
 // array (88 % busy, vector ALU 55 %).
-// V4_RECPF: the per-interaction coefficient record of the sweep (DevTab::DIAREC, 19 words) is fetched ONE INTERACTION AHEAD by three scalar
+// Single precision: the per-interaction coefficient record of the sweep (DevTab::DIAREC, 19 words) is fetched ONE INTERACTION AHEAD by three scalar
 // loads at the top of an interaction and pinned in scalar registers at its end.  Left to itself the compiler sinks each scalar load to the
 // block of its first use: eight loads in six places per interaction, each with its s_waitcnt lgkmcnt(0) one or two instructions later -- the
 // scalar-cache latency exposed six times per interaction, and the LDS reads in flight drained with it (scalar loads return out of order).
 // The 19 + 19 registers come from moving the sweep's loop-invariant uniform weights (saturation filter, angular weights) to vector registers.
-#ifndef V4_RECPF
-#define V4_RECPF 1
-#endif
-// Double precision (V4_RECV = 2): two records are 76 scalar registers, so the record of THIS interaction is fetched by scalar loads issued
+// Double precision: two records are 76 scalar registers, so the record of THIS interaction is fetched by scalar loads issued
 // together at its top and held there by a scheduling barrier: five loads in one place and 70 lgkmcnt(0) waits per eight interactions instead
-// of seven in six places and 91; - 4 % kernel time, bit-identical (0: as the compiler places them; the record one interaction ahead in vector
+// of seven in six places and 91; - 4 % kernel time, bit-identical (the record one interaction ahead in vector
 // registers was measured in round 5: + 28 % vector instructions, the same time -- profiles/r05_scalar_prefetch.txt).
-#ifndef V4_RECV
-#define V4_RECV 2
-#endif
-// Single precision only: in double precision the two records are 80 scalar registers, and the variant measured 3 % slower there.
+// The fetch one interaction ahead is single precision only: in double precision the two records are 80 scalar registers, and it measured 3 % slower there.
 // The builds with more live registers (48 directions: twelve filter weights; the RARE builds) spill to scratch with it and stay without.
 template <bool ON, typename T>
 __device__ __forceinline__ T v4_vreg(T x) {      // a wave-uniform value moved to a vector register on purpose
@@ -385,7 +376,6 @@ struct V4Adv {
   // OBSCOR(1:4) that scale the space weights of the neighbours (ctuw.F90:703-733)
   const T* obs;
   int m0, m1;           // advected frequencies [m0, m1); the others are carried over
-  int xcd_walk;         // XCD-aware order of the workgroups (diagnostics: measured 1 % slower than the natural order, profiles/r06_fused_*.txt)
 };
 template <typename T, int NANG, int PP, int MODE, int NSCR>
 __device__ __forceinline__ void v4_advect_tile(const V4Adv<T>& A, int ij0, int n, int lane, T* __restrict__ sT, T* __restrict__ sScr) {
@@ -404,7 +394,7 @@ __device__ __forceinline__ void v4_advect_tile(const V4Adv<T>& A, int ij0, int n
   constexpr bool LF = (MODE & 3) == 3;                 // fast waves with their own time step, read from compact rows
   constexpr bool OBS = (MODE & 4) != 0;                // sub-grid obstructions: three more 16-byte loads per step (the coefficients of the step's neighbours)
   constexpr int NB = OBS ? 11 : 8;
-  static_assert(MODE == 2 || (MODE & 1), "modes: 1 plain, 3 fast waves, + 4 obstructions; 2 the probe");
+  static_assert(MODE & 1, "modes: 1 plain, 3 fast waves, + 4 obstructions");
   constexpr int NKW = NANG * 4 + 4 + (LF ? NANG * 2 : 0);      // (LF: then [NANG][2]: 2 SP, 2 SM for DELPRO_LF)
   int* sI = reinterpret_cast<int*>(sK + NKW);          // [PP][16]: ij, KLON(1:2), KLAT(1:2,1:2), KCOR(1:4,1:2)
   int* sD = sI + PP * 16;                              // [NANG][4]
@@ -510,64 +500,59 @@ __device__ __forceinline__ void v4_advect_tile(const V4Adv<T>& A, int ij0, int n
     const Rnd& o = R[round_of(c)];
     const int q = c < NFULL * PP ? c % PP : o.q, k = o.k, m = o.m;
     T r[VEC];
-    if constexpr (MODE == 2) {
-#pragma unroll
-      for (int i = 0; i < VEC; i++) r[i] = T(0.3) * b[0][i] + T(0.1) * (((b[1][i] + b[2][i]) + (b[3][i] + b[4][i])) + ((b[5][i] + b[6][i]) + b[7][i]));
-    } else {
-      const int jx0 = o.jx0, jy0 = o.jy0, kc = o.kc;
-      const T* pq = sPt + q * PTW;
-      const T zd = pq[0], acpm1 = pq[1], ga = pq[2], tanph = pq[3], wl = pq[6 + jy0], omwl = pq[12 + jy0], wc = pq[8 + kc], omwc = pq[14 + kc];
-      const VT kk = *reinterpret_cast<const VT*>(sK + 4 * k);      // (double precision: two 16-byte reads)
-      const T kk2 = sizeof(T) == 4 ? kk[2 % VEC] : sK[4 * k + 2], kk3 = sizeof(T) == 4 ? kk[3 % VEC] : sK[4 * k + 3];
+    const int jx0 = o.jx0, jy0 = o.jy0, kc = o.kc;
+    const T* pq = sPt + q * PTW;
+    const T zd = pq[0], acpm1 = pq[1], ga = pq[2], tanph = pq[3], wl = pq[6 + jy0], omwl = pq[12 + jy0], wc = pq[8 + kc], omwc = pq[14 + kc];
+    const VT kk = *reinterpret_cast<const VT*>(sK + 4 * k);      // (double precision: two 16-byte reads)
+    const T kk2 = sizeof(T) == 4 ? kk[2 % VEC] : sK[4 * k + 2], kk3 = sizeof(T) == 4 ? kk[3 % VEC] : sK[4 * k + 3];
 #if ECWAM_HIP_CTU_STRICT
-      T a2, b2, p2, m2;
-      {
+    T a2, b2, p2, m2;
+    {
 #pragma clang fp contract(off)
-        const T tsp2 = tanph * kk[0], tsm2 = tanph * kk[1];
-        a2 = m_max(tsp2, T(0)); p2 = m_max(-tsp2, T(0)); b2 = m_max(-tsm2, T(0)); m2 = m_max(tsm2, T(0));
-      }
+      const T tsp2 = tanph * kk[0], tsm2 = tanph * kk[1];
+      a2 = m_max(tsp2, T(0)); p2 = m_max(-tsp2, T(0)); b2 = m_max(-tsm2, T(0)); m2 = m_max(tsm2, T(0));
+    }
 #else
-      T ab2, p2, m2;
-      ctu_fast_dir<T>(tanph, kk[0], kk[1], ab2, p2, m2);
-      T ab2_lf = ab2, p2_lf = p2, m2_lf = m2;
-      if constexpr (LF) ctu_fast_dir<T>(tanph, sK[NANG * 4 + 4 + 2 * k], sK[NANG * 4 + 4 + 2 * k + 1], ab2_lf, p2_lf, m2_lf);
+    T ab2, p2, m2;
+    ctu_fast_dir<T>(tanph, kk[0], kk[1], ab2, p2, m2);
+    T ab2_lf = ab2, p2_lf = p2, m2_lf = m2;
+    if constexpr (LF) ctu_fast_dir<T>(tanph, sK[NANG * 4 + 4 + 2 * k], sK[NANG * 4 + 4 + 2 * k + 1], ab2_lf, p2_lf, m2_lf);
 #endif
-      const T* bb = sB + q * 5 * NFRE + m;
-      const VT bha = *reinterpret_cast<const VT*>(bb + jx0 * NFRE), bhb = *reinterpret_cast<const VT*>(bb + (1 - jx0) * NFRE),
-               bya = *reinterpret_cast<const VT*>(bb + (2 + jy0) * NFRE), byb = *reinterpret_cast<const VT*>(bb + (3 - jy0) * NFRE),
-               bc0 = *reinterpret_cast<const VT*>(bb + 4 * NFRE);
+    const T* bb = sB + q * 5 * NFRE + m;
+    const VT bha = *reinterpret_cast<const VT*>(bb + jx0 * NFRE), bhb = *reinterpret_cast<const VT*>(bb + (1 - jx0) * NFRE),
+             bya = *reinterpret_cast<const VT*>(bb + (2 + jy0) * NFRE), byb = *reinterpret_cast<const VT*>(bb + (3 - jy0) * NFRE),
+             bc0 = *reinterpret_cast<const VT*>(bb + 4 * NFRE);
 #if ECWAM_HIP_CTU_STRICT
-      static_assert(!LF && !OBS, "the strict build of the weights has the plain form only");
+    static_assert(!LF && !OBS, "the strict build of the weights has the plain form only");
 #pragma unroll
-      for (int i = 0; i < VEC; i += 2) {
+    for (int i = 0; i < VEC; i += 2) {
 #define P2(a) V2<T>{a[i], a[i + 1]}
-        const V2<T> rr = ctu_w8_stencil_abs<T>(P2(bha), P2(bhb), P2(bya), P2(byb), P2(bc0), kk2, kk3, acpm1, zd, A.xdella, ga, A.delpro, cmtodeg, wl, omwl,
-                                               wc, omwc, a2, b2, p2, m2, P2(b[0]), P2(b[1]), P2(b[2]), P2(b[3]), P2(b[4]), P2(b[5]), P2(b[6]), P2(b[7]));
+      const V2<T> rr = ctu_w8_stencil_abs<T>(P2(bha), P2(bhb), P2(bya), P2(byb), P2(bc0), kk2, kk3, acpm1, zd, A.xdella, ga, A.delpro, cmtodeg, wl, omwl,
+                                             wc, omwc, a2, b2, p2, m2, P2(b[0]), P2(b[1]), P2(b[2]), P2(b[3]), P2(b[4]), P2(b[5]), P2(b[6]), P2(b[7]));
 #undef P2
-        r[i] = rr.x; r[i + 1] = rr.y;
-      }
+      r[i] = rr.x; r[i + 1] = rr.y;
+    }
 #else
-      const T zdg = pq[18], xdg = pq[19];
+    const T zdg = pq[18], xdg = pq[19];
 #pragma unroll
-      for (int i = 0; i < VEC; i += 2) {
+    for (int i = 0; i < VEC; i += 2) {
 #define P2(a) V2<T>{a[i], a[i + 1]}
-        const bool lf0 = LF && (m + i) < A.mlf, lf1 = LF && (m + i + 1) < A.mlf;
-        CtuFastW8<T> w = ctu_fast_w8<T>(P2(bha), P2(bhb), P2(bya), P2(byb), P2(bc0), kk2, kk3, zd, A.xdella, ga, zdg, xdg, wl, omwl, wc, omwc,
-                                        V2<T>{lf0 ? ab2_lf : ab2, lf1 ? ab2_lf : ab2}, V2<T>{lf0 ? p2_lf : p2, lf1 ? p2_lf : p2},
-                                        V2<T>{lf0 ? m2_lf : m2, lf1 ? m2_lf : m2});
-        if constexpr (OBS) {      // as k_propags2_otf: after the weights, before the stencil
-          w.wlon = w.wlon * P2(b[8]); w.wlat1 = w.wlat1 * P2(b[9]); w.wlat2 = w.wlat2 * P2(b[9]); w.wcor1 = w.wcor1 * P2(b[10]); w.wcor2 = w.wcor2 * P2(b[10]);
-        }
-        const V2<T> rr = ctu_fast_apply<T>(w, P2(b[0]), P2(b[1]), P2(b[2]), P2(b[3]), P2(b[4]), P2(b[5]), P2(b[6]), P2(b[7]));
+      const bool lf0 = LF && (m + i) < A.mlf, lf1 = LF && (m + i + 1) < A.mlf;
+      CtuFastW8<T> w = ctu_fast_w8<T>(P2(bha), P2(bhb), P2(bya), P2(byb), P2(bc0), kk2, kk3, zd, A.xdella, ga, zdg, xdg, wl, omwl, wc, omwc,
+                                      V2<T>{lf0 ? ab2_lf : ab2, lf1 ? ab2_lf : ab2}, V2<T>{lf0 ? p2_lf : p2, lf1 ? p2_lf : p2},
+                                      V2<T>{lf0 ? m2_lf : m2, lf1 ? m2_lf : m2});
+      if constexpr (OBS) {      // as k_propags2_otf: after the weights, before the stencil
+        w.wlon = w.wlon * P2(b[8]); w.wlat1 = w.wlat1 * P2(b[9]); w.wlat2 = w.wlat2 * P2(b[9]); w.wcor1 = w.wcor1 * P2(b[10]); w.wcor2 = w.wcor2 * P2(b[10]);
+      }
+      const V2<T> rr = ctu_fast_apply<T>(w, P2(b[0]), P2(b[1]), P2(b[2]), P2(b[3]), P2(b[4]), P2(b[5]), P2(b[6]), P2(b[7]));
 #undef P2
-        r[i] = rr.x; r[i + 1] = rr.y;
-      }
+      r[i] = rr.x; r[i + 1] = rr.y;
+    }
 #endif
-      if (carry) {
+    if (carry) {
 #pragma unroll
-        for (int i = 0; i < VEC; i++)
-          if (m + i < A.m0 || m + i >= A.m1) r[i] = b[0][i];      // outside the advected range: carried over
-      }
+      for (int i = 0; i < VEC; i++)
+        if (m + i < A.m0 || m + i >= A.m1) r[i] = b[0][i];      // outside the advected range: carried over
     }
     T* d = sT + m * RS + q * NANG + k;
 #pragma unroll
@@ -578,30 +563,28 @@ __device__ __forceinline__ void v4_advect_tile(const V4Adv<T>& A, int ij0, int n
 #pragma unroll
   for (int c = 0; c < D - 1 && c < NCH; c++) issue(c, buf[c % D]);
   __builtin_amdgcn_sched_barrier(0);
-  if constexpr ((MODE & 1) != 0) {
-    for (int i = lane; i < PP * NFRE; i += 64) {
-      const int q = i / NFRE, m = i - q * NFRE;
-      const int* iq = sI + q * 16;
-      const T* pq = sPt + q * PTW;
-      T cgl[2], cgy0[2], cgy1[2];
+  for (int i = lane; i < PP * NFRE; i += 64) {
+    const int q = i / NFRE, m = i - q * NFRE;
+    const int* iq = sI + q * 16;
+    const T* pq = sPt + q * PTW;
+    T cgl[2], cgy0[2], cgy1[2];
 #pragma unroll
-      for (int ic = 0; ic < 2; ic++) {
-        cgl[ic] = A.cg[(size_t)iq[1 + ic] * NFRE + m];
-        cgy0[ic] = A.cg[(size_t)iq[3 + 2 * ic] * NFRE + m];
-        cgy1[ic] = A.cg[(size_t)iq[4 + 2 * ic] * NFRE + m];
-      }
-      const T wl[2] = {pq[6], pq[7]}, dp[2] = {pq[4], pq[5]};
-      const CtuBase<T> b = ctu_base(A.cg[(size_t)iq[0] * NFRE + m], cgl, cgy0, cgy1, wl, dp);
-      T* o = sB + q * 5 * NFRE + m;
-#if ECWAM_HIP_CTU_STRICT
-      o[0] = m_abs(b.h[0]); o[NFRE] = m_abs(b.h[1]); o[2 * NFRE] = m_abs(b.hy[0]); o[3 * NFRE] = m_abs(b.hy[1]); o[4 * NFRE] = b.cg0;
-#else
-      ctu_fast_planes<T>(b, pq[1], ((LF && m < A.mlf) ? A.delpro_lf : A.delpro) * sK[NANG * 4], o, o + NFRE, o + 2 * NFRE, o + 3 * NFRE);
-      o[4 * NFRE] = b.cg0;
-#endif
+    for (int ic = 0; ic < 2; ic++) {
+      cgl[ic] = A.cg[(size_t)iq[1 + ic] * NFRE + m];
+      cgy0[ic] = A.cg[(size_t)iq[3 + 2 * ic] * NFRE + m];
+      cgy1[ic] = A.cg[(size_t)iq[4 + 2 * ic] * NFRE + m];
     }
-    WSYNC();
+    const T wl[2] = {pq[6], pq[7]}, dp[2] = {pq[4], pq[5]};
+    const CtuBase<T> b = ctu_base(A.cg[(size_t)iq[0] * NFRE + m], cgl, cgy0, cgy1, wl, dp);
+    T* o = sB + q * 5 * NFRE + m;
+#if ECWAM_HIP_CTU_STRICT
+    o[0] = m_abs(b.h[0]); o[NFRE] = m_abs(b.h[1]); o[2 * NFRE] = m_abs(b.hy[0]); o[3 * NFRE] = m_abs(b.hy[1]); o[4 * NFRE] = b.cg0;
+#else
+    ctu_fast_planes<T>(b, pq[1], ((LF && m < A.mlf) ? A.delpro_lf : A.delpro) * sK[NANG * 4], o, o + NFRE, o + 2 * NFRE, o + 3 * NFRE);
+    o[4 * NFRE] = b.cg0;
+#endif
   }
+  WSYNC();
 #pragma unroll
   for (int c = 0; c < NCH; c++) {
     if (c + D - 1 < NCH) issue(c + D - 1, buf[(c + D - 1) % D]);
@@ -609,9 +592,6 @@ __device__ __forceinline__ void v4_advect_tile(const V4Adv<T>& A, int ij0, int n
     finish(c, buf[c % D]);
     __builtin_amdgcn_sched_barrier(0);
   }
-#if defined(V4_ADV_PRIO)
-  __builtin_amdgcn_s_setprio(0);
-#endif
   WSYNC();
 }
 
@@ -780,8 +760,8 @@ __device__ void v4_sinput(const DevTab<T>& tb, const V4Ctx<T, NANG, PP>& L, T UF
   V2<T> f_n = *reinterpret_cast<const V2<T>*>(tF);
   V2<T> cw_n = *reinterpret_cast<const V2<T>*>(L.fac4 + Q4_CINV);
   T zcn_n = L.zcn[0];
-  // V4_RECPF: the row's record of module constants one row ahead as well (its scalar load would otherwise be waited for where it is issued)
-  constexpr bool RPF = (V4_RECPF != 0) && sizeof(T) == 4;
+  // single precision: the row's record of module constants one row ahead as well (its scalar load would otherwise be waited for where it is issued)
+  constexpr bool RPF = sizeof(T) == 4;
   T rw_n[6];
   if constexpr (RPF) {
 #pragma unroll
@@ -866,9 +846,9 @@ __device__ void v4_sinput(const DevTab<T>& tb, const V4Ctx<T, NANG, PP>& L, T UF
     sp = AVG * sp;
     fl = AVG * fl;
     T xrow = T(0), yrow = T(0);
-    // V4_REDN (single precision, where the branch above is always taken): the all-reduces of the row -- the stress of each gust state and, in
+    // single precision (where the branch above is always taken): the all-reduces of the row -- the stress of each gust state and, in
     // the second call, the row's positive input -- in one batch: two LDS round trips per row instead of five
-    constexpr bool REDN = (V4_REDN != 0) && sizeof(T) == 4;
+    constexpr bool REDN = sizeof(T) == 4;
     if constexpr (REDN) {
       constexpr int NR = 2 * NGST + (LLSNEG ? 1 : 0);
       T red[NR];
@@ -967,7 +947,7 @@ __device__ void v4_sinput_n(const DevTab<T>& tb, const V4Ctx<T, NANG, PP>& L, co
   const V2<T> rcos = {f_rcp(coswdif.x), f_rcp(coswdif.y)};
   T GAMNORMA[2] = {T(1), T(1)};
   const T* tF = L.tile + L.own;
-  constexpr bool RPF = (V4_RECPF != 0) && sizeof(T) == 4;      // the next row's module constants fetched ahead (see v4_sinput)
+  constexpr bool RPF = sizeof(T) == 4;      // the next row's module constants fetched ahead (see v4_sinput)
   T rw_n[6];
   if constexpr (RPF) {
 #pragma unroll
@@ -1098,7 +1078,7 @@ __device__ void v4_sinput_jan(const DevTab<T>& tb, const V4Ctx<T, NANG, PP>& L, 
 #pragma unroll
   for (int s = 0; s < NS; s++) { rX[s] = T(0); rY[s] = T(0); }
   const T* tF = L.tile + L.own;
-  constexpr bool RPF = (V4_RECPF != 0) && sizeof(T) == 4;      // the next row's module constants fetched ahead (see v4_sinput)
+  constexpr bool RPF = sizeof(T) == 4;      // the next row's module constants fetched ahead (see v4_sinput)
   T rw_n[6];
   if constexpr (RPF) {
 #pragma unroll
@@ -1294,17 +1274,10 @@ k_implsch4(const DevTab<T>* __restrict__ tp, int kijs, int kijl, T* __restrict__
     }
   }
   const int p = L.p, j = L.j;
-  // ADV: the workgroups of a launch are dealt round-robin to the 8 XCDs; XCD x takes the contiguous eighth [x gridDim.x / 8, ...) of the
-  // wave's triples so that a row fetched as somebody's neighbour is met again in the same L2 (gridDim.x is a multiple of 8)
-  // (xcd_walk = G > 1: groups of G consecutive waves per XCD, the groups of the 8 XCDs interleaved -- the chip still moves through the grid as
-  // one front; gridDim.x is then a multiple of 8 G)
-  int blk = (int)blockIdx.x;
-  if (ADV != 0 && adv.xcd_walk == 1) blk = (int)(blockIdx.x & 7u) * (int)(gridDim.x >> 3) + (int)(blockIdx.x >> 3);
-  else if (ADV != 0 && adv.xcd_walk > 1) {
-    const int G_ = adv.xcd_walk, x_ = (int)(blockIdx.x & 7u), j_ = (int)(blockIdx.x >> 3);
-    blk = (j_ / G_) * (8 * G_) + x_ * G_ + (j_ % G_);
-  }
-  const int ij0 = kijs + blk * PP;
+  // The workgroups take the points in the natural order, ADV builds included: consecutive workgroups go round-robin to the 8 XCDs, so the chip
+  // moves through the grid as one front.  (An XCD-aware order -- a contiguous eighth of the grid per XCD, so that a row fetched as somebody's
+  // neighbour is met again in the same L2 -- measured 1 % slower: profiles/r06_fused_step_experiments.txt.)
+  const int ij0 = kijs + (int)blockIdx.x * PP;
   if (ij0 >= kijl) return;
   const int n = kijl - ij0 < PP ? kijl - ij0 : PP;   // points of this wave; a short last wave replicates its last point
   const int ij = ij0 + (p < n ? p : n - 1);
@@ -1342,9 +1315,9 @@ k_implsch4(const DevTab<T>* __restrict__ tp, int kijs, int kijl, T* __restrict__
     L.rDFIM = tb.DFIM[mi]; L.rDFIMOFR = tb.DFIMOFR[mi]; L.rDFIMFR = tb.DFIMFR[mi]; L.rZPIFR = tb.ZPIFR[mi]; L.rRHOWG = tb.RHOWG_DFIM[mi];
     L.rCOFRM4 = tb.COFRM4[mi]; L.rFLMAX = tb.FLMAX[mi];
   }
-  // V4_RECPF: the module constants of a row from the lane-held copies of the tables above (v_readlane) instead of a scalar load per row
+  // single precision: the module constants of a row from the lane-held copies of the tables above (v_readlane) instead of a scalar load per row
   // that is waited for where it is issued (the row loops of SDEPTHLIM / FKMEAN and FEMEANWS)
-  constexpr bool RLANE = (V4_RECPF != 0) && sizeof(T) == 4;
+  constexpr bool RLANE = sizeof(T) == 4;
   L.sinth = V2<T>{tb.SINTH[2 * j], tb.SINTH[2 * j + 1]};
   L.costh = V2<T>{tb.COSTH[2 * j], tb.COSTH[2 * j + 1]};
   T* c = L.c;
@@ -1966,7 +1939,7 @@ k_implsch4(const DevTab<T>* __restrict__ tp, int kijs, int kijl, T* __restrict__
     const T DAL1 = tb.DAL1, DAL2 = tb.DAL2;
     const T CL11 = tb.DIAANG[0], ACL1 = tb.DIAANG[1], CL21 = tb.DIAANG[2], ACL2 = tb.DIAANG[3];
     const T CL11Q = tb.DIAANG[4], ACL1Q = tb.DIAANG[5], CL21Q = tb.DIAANG[6], ACL2Q = tb.DIAANG[7];
-    constexpr bool RECPF_ON = (V4_RECPF != 0) && sizeof(T) == 4 && NANG <= 36 && !RARE;      // (see V4_RECPF)
+    constexpr bool RECPF_ON = sizeof(T) == 4 && NANG <= 36 && !RARE;      // (the record fetched one interaction ahead: see v4_vreg)
     T wt[NH + 1];   // SATWEIGHTS depend on the tap only and are symmetric (checked by ecwam_hip_create): wave-uniform, taps -NH .. 0
 #pragma unroll
     for (int t = 0; t <= NH; t++) wt[t] = v4_vreg<RECPF_ON>(tb.SATWEIGHTS[t][NANG / 2]);
@@ -2110,9 +2083,9 @@ k_implsch4(const DevTab<T>* __restrict__ tp, int kijs, int kijl, T* __restrict__
     const int UPD_LIM = whole ? NFRE : mijmax;                                      // rows m < UPD_LIM (0-based) are updated
     const int DIA_LIM = whole ? MLST : (mijmax + 4 < MLST ? mijmax + 4 : MLST);     // interactions MC <= DIA_LIM contribute to them
     const int MC_END = whole ? MLST : (mijmax + 5 < MLST ? mijmax + 5 : MLST);      // row MIJ is updated at the top of interaction MIJ + 5
-    // V4_RECV = 2 (double precision): the record of THIS interaction by scalar loads issued together at its top and held there (one
+    // double precision: the record of THIS interaction by scalar loads issued together at its top and held there (one
     // register set: two are 76 scalar registers) -- one wait per interaction instead of six
-    constexpr bool RECS = !RARE && (V4_RECV == 2) && sizeof(T) == 8;      // (sp at 48 directions: its spilled scalar registers push the vector registers past 256)
+    constexpr bool RECS = !RARE && sizeof(T) == 8;      // (sp at 48 directions: its spilled scalar registers push the vector registers past 256)
     constexpr bool RECPF = (RECPF_ON || RECS);
     T ra[20], rb[20];      // RECPF: the records of two consecutive interactions, roles alternating (the loop is unrolled by eight: static)
     if constexpr (RECPF) {

@@ -311,8 +311,7 @@ int ecwam_hip_implsch_reserve(ecwam_hip_ctx *ctx, int npts);
  * Covered: what ecwam_hip_propags2_implsch_supported reports (48 / 36 / 24 / 12 directions x 36 frequencies in single, 36 x 36 in double precision, the common builds of
  * IMPLSCH with IPHYS = 1 / ISNONLIN = 0, no refraction; with or without the obstructions of ecwam_hip_set_obstructions); everything else runs
  * the two calls.
- * flags: 0 (bit 0: workgroups in the XCD-aware order of the stencil kernel instead of the natural one; bit 1: the go / no-go probe of
- * diagnostics builds).
+ * flags: 0 only.
  */
 /* 0: no one-kernel build covers the context; else a mask: bit 0 the plain step, bit 1 also with fast waves (gin), bit 2 also with obstructions */
 int ecwam_hip_propags2_implsch_supported(ecwam_hip_ctx *ctx);

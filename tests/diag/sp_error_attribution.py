@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Where the single-precision difference between k_implsch4 and the oracle comes from (diagnostic, not a test).
 
-For every build variant of the IMPLSCH translation units (ecwam_amd/build.py VARIANTS: hardware reciprocal / square root, hardware
-exp2 / log2 with a one-product argument scaling, FMA contraction) one fresh process loads that library (ECWAM_HIP_LIB) and reports
+For the product and every numeric build variant of the IMPLSCH translation units (DEFAULT_VARIANTS below, keys of ecwam_amd/build.py
+VARIANTS: hardware reciprocal / square root, hardware exp2 / log2 with a one-product argument scaling, FMA contraction) one fresh process loads that library (ECWAM_HIP_LIB) and reports
   * the parity statistics of one IMPLSCH call against the oracle (1 536 points, 36 x 36, mixed sea and swell, IDELT = 900 and 450 s),
   * the per-point swh difference after 12 full WAMINTGR steps on a small grid with land (24 x 29, IDELT = 900 s),
   * the time of an IMPLSCH launch on 131 072 points.
@@ -19,6 +19,8 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 
 ORACLE_ROW = "--oracle-row" in sys.argv
+# what runs without arguments: the product and the variants that change its arithmetic (ECWAM_HIP_STRICT of csrc/dev.h, the IEEE mode)
+DEFAULT_VARIANTS = ["", "exactdiv", "strict1", "strict2", "site4", "site8", "site32", "strict3", "strict7", "noieee"]
 
 
 def worker() -> None:
@@ -113,10 +115,12 @@ def worker() -> None:
 def main() -> None:
     from ecwam_amd import build as B
 
-    variants = [a for a in sys.argv[1:] if not a.startswith("--")] or list(B.VARIANTS)
+    variants = ["" if a in ("default", "product") else a for a in sys.argv[1:] if not a.startswith("--")] or DEFAULT_VARIANTS
+    unknown = [v for v in variants if v not in B.VARIANTS]
+    if unknown:
+        sys.exit(f"unknown build variant(s) {unknown}: {sorted(B.VARIANTS)}")
     rows = []
     for v in ["oracle-sp"] + variants:
-        v = "" if v in ("default", "product") else v
         env = dict(os.environ)
         if v != "oracle-sp":
             lib = B.lib_path(v)

@@ -173,7 +173,7 @@ def test_one_kernel_step_at_the_other_direction_counts(api, prec, nang, nfre_red
 
 
 def test_one_kernel_step_natural_order_and_row_blocks(api):
-    """The workgroups in the XCD-aware order (flags bit 0) and the rows passed in three unequal blocks give the same bits as one call."""
+    """The rows passed in three unequal blocks (the workgroups of every call in the natural order, the only one) give the same bits as one call."""
     from ecwam_amd import grid as G
 
     cfg = Config(nang=36, nfre=36, nfre_red=36, idelt=450, idelpro=450)
@@ -183,9 +183,34 @@ def test_one_kernel_step_natural_order_and_row_blocks(api):
     a.step_fused()
     b.newwind()
     n = b.n
-    for k0, k1, fl in ((0, 7, 1), (7, n // 2 + 1, 0), (n // 2 + 1, n, 1)):
-        b.ctx.propags2_implsch(b.fl1, b.fl3, b.gd, b.cgroup_ext, float(cfg.idelpro), k0, k1, b.wvprpt, b.ff, b.intf, b.mij, b.xllws, 1, cfg.nfre_red,
-                               flags=fl)
+    for k0, k1 in ((0, 7), (7, n // 2 + 1), (n // 2 + 1, n)):
+        b.ctx.propags2_implsch(b.fl1, b.fl3, b.gd, b.cgroup_ext, float(cfg.idelpro), k0, k1, b.wvprpt, b.ff, b.intf, b.mij, b.xllws, 1, cfg.nfre_red)
+    b.fl1, b.fl3 = b.fl3, b.fl1
+    torch.cuda.synchronize()
+    _same_state(a, b)
+    a.ctx.close(); b.ctx.close()
+
+
+def test_one_kernel_step_refuses_flags(api):
+    """ecwam_hip_propags2_implsch knows no flags (the order and probe switches of round 6 left the library): every bit is refused with a
+    message that names the flags, before any device work -- the output spectrum keeps its sentinel -- and the refused calls leave nothing
+    behind: the same context then steps with flags = 0 to the bits of a context that never saw them."""
+    from ecwam_amd import grid as G
+
+    cfg = Config(nang=36, nfre=36, nfre_red=36, idelt=450, idelpro=450)
+    g = G.build_grid(16, mask="continents")
+    a, b = _pair(cfg, g, seed=5)
+    assert a.build_weights() == 0 and b.build_weights() == 0
+    a.step_fused()
+    b.newwind()
+    b.fl3.fill_(-7.0)
+    for flags in (1, 2, 1 << 8):
+        with pytest.raises(api.EcwamHipError, match="ecwam_hip_propags2_implsch: unknown flags"):
+            b.ctx.propags2_implsch(b.fl1, b.fl3, b.gd, b.cgroup_ext, float(cfg.idelpro), 0, b.n, b.wvprpt, b.ff, b.intf, b.mij, b.xllws, 1, cfg.nfre_red,
+                                   flags=flags)
+        torch.cuda.synchronize()
+        assert bool((b.fl3 == -7.0).all())
+    b.ctx.propags2_implsch(b.fl1, b.fl3, b.gd, b.cgroup_ext, float(cfg.idelpro), 0, b.n, b.wvprpt, b.ff, b.intf, b.mij, b.xllws, 1, cfg.nfre_red, flags=0)
     b.fl1, b.fl3 = b.fl3, b.fl1
     torch.cuda.synchronize()
     _same_state(a, b)

@@ -1,6 +1,6 @@
 #!/bin/bash
 # diagnostics: timing of several builds of the library on the same GPU, IMPLSCH on 421 080 points, minimum of the launches of each of
-# four alternating runs.  usage: bash tools/ab3.sh sp <lib suffix> [<lib suffix> ...]   ("" = the product library, "base" = libecwam_hip_base.so ...)
+# four alternating runs.  usage: bash tools/ab3.sh sp <lib suffix> [<lib suffix> ...]   ("" = the product library, otherwise a key of ecwam_amd.build.VARIANTS)
 prec=$1; shift
 for i in 1 2 3 4; do
   for v in "$@"; do

@@ -1,5 +1,5 @@
 #!/bin/bash
-# diagnostics: LDS counters of IMPLSCH for several builds of the library on one box.  usage: bash tools/pmc_lds_variants.sh "" natlayout ...
+# diagnostics: LDS counters of IMPLSCH for several builds of the library on one box.  usage: bash tools/pmc_lds_variants.sh "" noieee ...   (keys of ecwam_amd.build.VARIANTS)
 for v in "$@"; do
   export ECWAM_HIP_LIB="${GRAFT_REPO_ROOT:?GRAFT_REPO_ROOT not set}"/ecwam_amd/lib/libecwam_hip${v:+_$v}.so
   echo "== ${v:-product}"
