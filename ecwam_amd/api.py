@@ -354,6 +354,49 @@ class HipContext:
                                                     self._real(out, (out.shape[0], len(OUTBS_ABS_FIELDS)), "OUT"),
                                                     opt(fl2nd, (0 if fl2nd is None else fl2nd.shape[0], self.NANG, self.NFRE), "FL2ND"), _stream_ptr()))
 
+    # -- LSECONDORDER: the tables of SECONDHH_GEN / TABLES_2ND (ecwam_amd.second_order.SecondOrderTables), or five arrays in their place
+    @property
+    def has_second_order(self) -> bool:
+        return getattr(self, "_second_order", False)
+
+    def set_second_order(self, so, coefficients=None) -> None:
+        """Upload the second-order tables (ecwam_hip_set_second_order).  so: a SecondOrderTables of this context's grid and precision, or
+        None to remove them.  coefficients: five arrays [NDEPTH][NANGH][NFREH][NFREH] used in place of so.TA, TB, TC_QL, TT_4M, TT_4P."""
+        self._second_order = False      # the library drops its tables first: a failed upload leaves none
+        if so is None:
+            self._chk(self.lib.ecwam_hip_set_second_order(self._h, 0, 1.0, 1.1, 0, None, None, None, None, None, None, None))
+            return
+        dt = self.t.dtype
+        if so.dtype != dt or so.NANGH * 2 != self.NANG or so.NFREH * 2 != self.NFRE:
+            raise ValueError("second-order tables of another grid or precision")
+        tabs = [getattr(so, c) for c in so.COEFFICIENTS] if coefficients is None else list(coefficients)
+        shape = (so.NDEPTH, so.NANGH, so.NFREH, so.NFREH)
+        # the C interface takes the reference's storage order TA(JD,L,M1,M): C order [M][M1][L][JD]
+        host = [np.ascontiguousarray(np.asarray(a, dt).reshape(shape).transpose(3, 2, 1, 0)) for a in tabs]
+        imp = np.ascontiguousarray(so.IM_P.T.astype(np.int32))
+        imm = np.ascontiguousarray(so.IM_M.T.astype(np.int32))
+        self._chk(self.lib.ecwam_hip_set_second_order(self._h, so.NDEPTH, float(so.DEPTHA), float(so.DEPTHD), so.NMAX, imp.ctypes.data, imm.ctypes.data,
+                                                      *[a.ctypes.data for a in host]))
+        self._second_order = True
+
+    def outbs_second_order(self, kijs, kijl, fl1, wvprpt, depth, ucur, vcur, ff, out, fl2nd=None, sig: float = 1.0, zmiss: float = -999.0):
+        """outbs_absolute with CAL_SECOND_ORDER_SPEC between INTPOL and the ice noise reshaping (ecwam_hip_outbs_second_order; LSECONDORDER = T):
+        out[:, 8] in the columns OUTBS_ABS_FIELDS.  depth: reals [>= kijl]; wvprpt is always needed; sig = -1 removes the correction.  Needs
+        set_second_order()."""
+        nrow = fl1.shape[0]
+        rows = [nrow, out.shape[0], wvprpt.shape[0], depth.shape[0]] + [a.shape[0] for a in (ucur, vcur, ff, fl2nd) if a is not None]
+        if not (0 <= kijs <= kijl <= min(rows)):
+            raise ValueError("OUTBS_SECOND_ORDER: KIJS/KIJL outside the operands")
+        opt = lambda a, shape, name: None if a is None else self._real(a, shape, name)
+        a = [self._real(fl1, (nrow, self.NANG, self.NFRE), "FL1"), self._real(wvprpt, (wvprpt.shape[0], NWPR, self.NFRE), "WVPRPT"),
+             self._real(depth, (depth.shape[0],), "DEPTH"),
+             opt(ucur, (0 if ucur is None else ucur.shape[0],), "UCUR"), opt(vcur, (0 if vcur is None else vcur.shape[0],), "VCUR"),
+             opt(ff, (0 if ff is None else ff.shape[0], NFF), "FF")]
+        self._chk(self.lib.ecwam_hip_outbs_second_order(self._h, kijs, kijl, *a, float(sig), float(zmiss),
+                                                        self._real(out, (out.shape[0], len(OUTBS_ABS_FIELDS)), "OUT"),
+                                                        opt(fl2nd, (0 if fl2nd is None else fl2nd.shape[0], self.NANG, self.NFRE), "FL2ND"),
+                                                        _stream_ptr()))
+
     def outwnorm(self, field, column: int, n: int, zmiss: float = -999.0):
         """(average, minimum, maximum, count) of field[:n, column] over the values != zmiss."""
         if not (field.is_cuda and field.dtype == self.dtype and field.is_contiguous() and field.dim() == 2 and n <= field.shape[0]):

@@ -67,6 +67,13 @@ struct ecwam_hip_ctx {
   void* adv_pt = nullptr;     // [npts][12]
   size_t adv_pt_bytes = 0;
   void* adv_dir = nullptr;    // reals [4 NANG + 4], then ints [4 NANG]
+  // LSECONDORDER (ecwam_hip_set_second_order; csrc/outbs_2nd.hip): SoTab<T>, the coefficient tables [JD][M][M1][5][NANGH], the work space
+  void* so_tab = nullptr;
+  void* so_coef = nullptr;
+  void* so_work = nullptr;
+  size_t so_work_bytes = 0;
+  int so_nmax = 0;
+  std::vector<unsigned char> fr_host;  // FR(1:NFRE) in the working precision
   const void* obs = nullptr;  // LSUBGRID: device OBS[n_obs][8][NFRE] (ecwam_hip_set_obstructions), read by CTUW / PROPAGS2
   int n_obs = 0;
 };
@@ -88,6 +95,11 @@ template <typename T> int launch_outbs_partition(const void*, int, int, const vo
 template <typename T> int launch_outbs_extremes(const void*, int, int, const void*, const void*, const void*, int, void*, int, int, hipStream_t);
 template <typename T> int launch_outbs_absolute(const void*, const void*, int, int, int, const void*, const void*, const void*, const void*, const void*,
                                                  double, void*, void*, int, int, hipStream_t);
+template <typename T> int launch_outbs_second_order(const void*, const void*, const void*, const void*, void*, int, int, int, int, const void*, const void*,
+                                                     const void*, const void*, const void*, const void*, double, double, void*, void*, int, int, hipStream_t);
+const char* so_tab_build(const ecwam_hip_params*, const void*, int, int, double, double, int, const int*, const int*, std::vector<unsigned char>&);
+void so_coef_layout(int, int, int, int, const void* const[5], std::vector<unsigned char>&);
+size_t so_work_bytes(int, int, int, int, int);
 size_t intpol_tab_build(const ecwam_hip_params*, const ecwam_hip_tables*, int, std::vector<unsigned char>&);
 template <typename T> void launch_norm(const void*, int, int, double, double*, int, hipStream_t);
 template <typename T> void launch_newwind(const void*, int, void*, const void*, int, hipStream_t);
@@ -469,6 +481,7 @@ int ecwam_hip_create(const ecwam_hip_params* p, const ecwam_hip_tables* t, int r
   HIPCHK(hipSetDevice(device));
   ecwam_hip_ctx* c = new ecwam_hip_ctx();
   c->real_bytes = real_bytes; c->device = device; c->NANG = p->nang; c->NFRE = p->nfre; c->NFRE_RED = p->nfre_red; c->p = *p;
+  c->fr_host.assign((const unsigned char*)t->fr, (const unsigned char*)t->fr + (size_t)p->nfre * real_bytes);
 #define HIPCHK_CTX(x)                                                                              \
   do {                                                                                             \
     hipError_t e_ = (x);                                                                           \
@@ -521,6 +534,9 @@ int ecwam_hip_destroy(ecwam_hip_ctx* c) {
   if (c->dtab) (void)hipFree(c->dtab);
   if (c->norm_scratch) (void)hipFree(c->norm_scratch);
   if (c->itab) (void)hipFree(c->itab);
+  if (c->so_tab) (void)hipFree(c->so_tab);
+  if (c->so_coef) (void)hipFree(c->so_coef);
+  if (c->so_work) (void)hipFree(c->so_work);
   if (c->fin) (void)hipFree(c->fin);
   if (c->wi) (void)hipFree(c->wi);
   if (c->adv_pt) (void)hipFree(c->adv_pt);
@@ -991,6 +1007,64 @@ int ecwam_hip_outbs_absolute(ecwam_hip_ctx* c, int kijs, int kijl, const void* f
   DISPATCH(rc = launch_outbs_absolute<float>(c->dtab, c->itab, kijs, kijl, mode, fl1, wvprpt, ucur, vcur, ff, zmiss, out, fl2nd, c->NANG, c->NFRE, s),
            rc = launch_outbs_absolute<double>(c->dtab, c->itab, kijs, kijl, mode, fl1, wvprpt, ucur, vcur, ff, zmiss, out, fl2nd, c->NANG, c->NFRE, s));
   if (rc) return fail("ecwam_hip_outbs_absolute: unsupported spectral size");
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+int ecwam_hip_set_second_order(ecwam_hip_ctx* c, int ndepth, double deptha, double depthd, int nmax, const int* im_p, const int* im_m, const void* ta,
+                               const void* tb, const void* tc_ql, const void* tt_4m, const void* tt_4p) {
+  if (!c) return fail("null context");
+  HIPCHK(hipSetDevice(c->device));
+  HIPCHK(hipDeviceSynchronize());
+  if (c->so_tab) (void)hipFree(c->so_tab);
+  if (c->so_coef) (void)hipFree(c->so_coef);
+  c->so_tab = c->so_coef = nullptr;
+  c->so_nmax = 0;
+  if (!ta) return 0;
+  if (!im_p || !im_m || !tb || !tc_ql || !tt_4m || !tt_4p) return fail("ecwam_hip_set_second_order: null pointer");
+  std::vector<unsigned char> h, hc;
+  const char* why = so_tab_build(&c->p, c->fr_host.data(), c->real_bytes, ndepth, deptha, depthd, nmax, im_p, im_m, h);
+  if (why) return fail((std::string("ecwam_hip_set_second_order: ") + why).c_str());
+  const void* const src[5] = {ta, tb, tc_ql, tt_4m, tt_4p};
+  so_coef_layout(c->real_bytes, ndepth, c->NANG / 2, c->NFRE / 2, src, hc);
+  HIPCHK(hipMalloc(&c->so_tab, h.size()));
+  HIPCHK(hipMemcpy(c->so_tab, h.data(), h.size(), hipMemcpyHostToDevice));
+  HIPCHK(hipMalloc(&c->so_coef, hc.size()));
+  HIPCHK(hipMemcpy(c->so_coef, hc.data(), hc.size(), hipMemcpyHostToDevice));
+  c->so_nmax = nmax;
+  return 0;
+}
+
+int ecwam_hip_outbs_second_order(ecwam_hip_ctx* c, int kijs, int kijl, const void* fl1, const void* wvprpt, const void* depth, const void* ucur,
+                                 const void* vcur, const void* ff, double sig, double zmiss, void* out, void* fl2nd, void* stream) {
+  if (!c) return fail("null context");
+  if (kijl < kijs || kijs < 0) return fail("ecwam_hip_outbs_second_order: bad range");
+  if (!c->so_tab || !c->so_coef) return fail("ecwam_hip_outbs_second_order: the second-order tables are not set (ecwam_hip_set_second_order)");
+  const bool intpol = c->p.irefra >= 2, ice = c->p.licerun && !c->p.lmaskice;
+  if (kijl > kijs && (!fl1 || !out || !wvprpt || !depth)) return fail("ecwam_hip_outbs_second_order: null pointer (fl1, wvprpt, depth and out are needed)");
+  if (kijl > kijs && intpol && (!ucur || !vcur)) return fail("ecwam_hip_outbs_second_order: IREFRA = 2 / 3 needs ucur and vcur");
+  if (kijl > kijs && ice && !ff) return fail("ecwam_hip_outbs_second_order: LICERUN without LMASKICE needs ff (CICOVER, WSWAVE)");
+  if (fl2nd && fl2nd == fl1) return fail("ecwam_hip_outbs_second_order: FL1 and FL2ND must not alias");
+  if (intpol && !c->itab) return fail("ecwam_hip_outbs_second_order: NFRE_MAX of INTPOL exceeds the library's table");
+  if (!(sig == 1.0 || sig == -1.0)) return fail("ecwam_hip_outbs_second_order: SIG must be +1 or -1");
+  if (kijl == kijs) return 0;
+  hipStream_t s = (hipStream_t)stream;
+  const size_t need = so_work_bytes(c->real_bytes, kijl - kijs, c->NANG / 2, c->NFRE / 2, c->so_nmax);
+  if (need > c->so_work_bytes) {
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipDeviceSynchronize());
+    if (c->so_work) (void)hipFree(c->so_work);
+    c->so_work = nullptr; c->so_work_bytes = 0;
+    HIPCHK(hipMalloc(&c->so_work, need));
+    c->so_work_bytes = need;
+  }
+  const int mode = (intpol ? 1 : 0) | (ice ? 2 : 0);
+  int rc;
+  DISPATCH(rc = launch_outbs_second_order<float>(c->dtab, c->itab, c->so_tab, c->so_coef, c->so_work, c->so_nmax, kijs, kijl, mode, fl1, wvprpt, depth, ucur,
+                                                 vcur, ff, sig, zmiss, out, fl2nd, c->NANG, c->NFRE, s),
+           rc = launch_outbs_second_order<double>(c->dtab, c->itab, c->so_tab, c->so_coef, c->so_work, c->so_nmax, kijs, kijl, mode, fl1, wvprpt, depth, ucur,
+                                                  vcur, ff, sig, zmiss, out, fl2nd, c->NANG, c->NFRE, s));
+  if (rc) return fail("ecwam_hip_outbs_second_order: unsupported spectral size (NANG must be 48, 36, 24 or 12)");
   HIPCHK(hipGetLastError());
   return 0;
 }

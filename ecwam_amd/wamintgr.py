@@ -612,6 +612,22 @@ class Wamintgr:
         self.ctx.outbs_absolute(0, self.n, self.fl1, self.wvprpt, u, v, self.ff, out, fl2nd=fl2nd)
         return (out, fl2nd) if store_spectrum else out
 
+    # ---- the same with LSECONDORDER = T (CAL_SECOND_ORDER_SPEC between INTPOL and the ice reshaping).  The tables of SECONDHH_GEN /
+    # TABLES_2ND are built and uploaded on first use.  depth [n]: DEPTH of the points; default: the model's own depth with refraction,
+    # else BATHYMAX = 999 m everywhere (the deep-water set-up this driver runs without IREFRA)
+    def outbs_second_order(self, store_spectrum: bool = False, depth=None, sig: float = 1.0):
+        if not self.ctx.has_second_order:
+            from .second_order import SecondOrderTables
+            self.second_order_tables = SecondOrderTables(self.t)
+            self.ctx.set_second_order(self.second_order_tables)
+        if depth is None:
+            depth = self.depth_ext if self.irefra else torch.full((self.n,), 999.0, dtype=self.dtype, device=self.dev)
+        out = torch.zeros((self.n, len(api.OUTBS_ABS_FIELDS)), dtype=self.dtype, device=self.dev)
+        fl2nd = torch.empty((self.n, self.cfg.nang, self.cfg.nfre), dtype=self.dtype, device=self.dev) if store_spectrum else None
+        u, v = (self.u_ext, self.v_ext) if self.irefra >= 2 else (None, None)
+        self.ctx.outbs_second_order(0, self.n, self.fl1, self.wvprpt, depth, u, v, self.ff, out, fl2nd=fl2nd, sig=sig)
+        return (out, fl2nd) if store_spectrum else out
+
     def swh_norm(self):
         return self.ctx.outwnorm(self.outbs(), 0, self.n)
 

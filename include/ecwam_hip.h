@@ -383,7 +383,7 @@ int ecwam_hip_outbs_partition(ecwam_hip_ctx *ctx, int kijs, int kijl, const void
  *   11 cmax_st space-time maximum crest CMAX_ST [80]         12 hmax_st space-time maximum height HMAX_ST [81]
  * flags: bit 0 -- KURTOSIS only: W_MAXH is skipped and columns 9-12 are not written (the reference calls W_MAXH only when one of
  * 78-81 is requested).  Other bits: error.  AKI's open iteration is bounded at 100 Newton steps.  Not served: the FL2ND transforms
- * (INTPOL, LSECONDORDER; KURTOSIS and W_MAXH read FL1), OUTSETWMASK, SIG_TH / EPS / XNU and PHIST (not OUTBLOCK parameters).
+ * (INTPOL, CAL_SECOND_ORDER_SPEC; KURTOSIS and W_MAXH read FL1), OUTSETWMASK, SIG_TH / EPS / XNU and PHIST (not OUTBLOCK parameters).
  * OUTWNORM statistics of a column: ecwam_hip_outwnorm(out + column, stride = 13).
  * The INTPOL transform and the ice noise reshaping of FL2ND, for the parameters that read FL2ND: ecwam_hip_outbs_absolute.
  */
@@ -408,11 +408,47 @@ int ecwam_hip_outbs_extremes(ecwam_hip_ctx *ctx, int kijs, int kijl, const void 
  * Columns 0-4 are bit for bit what ecwam_hip_outbs gives on FL2ND, columns 5-7 what ecwam_hip_outbs_sepwisw gives in its columns 0-2.
  * fl2nd (may be NULL): device FL2ND[npts][NANG][NFRE] that receives the rows [kijs,kijl) of the output spectrum (for SE10MEAN / SEBTMEAN,
  * spectral output or the host); with NULL nothing but out is written.  fl2nd must not overlap fl1 (fl2nd == fl1 is refused).  The scatter of INTPOL uses no atomics: results do not depend on
- * scheduling.  flags: 0 only.  The spectral sizes of ecwam_hip_outbs_sepwisw.  Not served: CAL_SECOND_ORDER_SPEC (LSECONDORDER),
- * OUTSETWMASK, IRA = -1.  OUTWNORM statistics of a column: ecwam_hip_outwnorm(out + column, stride = 8).
+ * scheduling.  flags: 0 only.  The spectral sizes of ecwam_hip_outbs_sepwisw.  CAL_SECOND_ORDER_SPEC (LSECONDORDER = T) is served by
+ * ecwam_hip_outbs_second_order.  Not served: OUTSETWMASK, IRA = -1.  OUTWNORM statistics of a column: ecwam_hip_outwnorm(out + column,
+ * stride = 8).
  */
 int ecwam_hip_outbs_absolute(ecwam_hip_ctx *ctx, int kijs, int kijl, const void *fl1, const void *wvprpt, const void *ucur, const void *vcur,
                              const void *ff, int flags, double zmiss, void *out, void *fl2nd, void *stream);
+
+/*
+ * The tables of the second-order output spectrum (LSECONDORDER = T; YOWTABL as SECONDHH_GEN and TABLES_2ND fill it, secondhh_gen.F90:73-121,
+ * tables_2nd.F90:107-186), for ecwam_hip_outbs_second_order.  Only the thinning SECONDHH_GEN always selects is served: NFREH = NFRE/2,
+ * NANGH = NANG/2, MR = MA = 2 (odd NANG or NFRE: refused).  All pointers are HOST arrays in the reference's storage order, copied before
+ * the call returns:
+ *   ndepth, deptha, depthd   NDEPTH, DEPTHA, DEPTHD of YOWSHAL (mpuserin.F90:616-618: 74, 1, 1.1)
+ *   nmax                     NMAX of YOWTABL (22 at NFRE = 36)
+ *   im_p, im_m               int IM_P(NFREH,NFREH), IM_M(NFREH,NFREH): values 1 .. NMAX, [M][M1] in C order
+ *   ta, tb, tc_ql, tt_4m, tt_4p   reals of the working precision, TA(NDEPTH,NANGH,NFREH,NFREH): [M][M1][L][JD] in C order
+ * OMEGA, OMEGA_EXT and the interpolation weights follow from FR and FRATIO of ecwam_hip_create.  ta == NULL removes the tables.  The device
+ * layout is the library's own (one contiguous slice per depth index).  Not thread safe against calls in flight on the context.
+ */
+int ecwam_hip_set_second_order(ecwam_hip_ctx *ctx, int ndepth, double deptha, double depthd, int nmax, const int *im_p, const int *im_m,
+                               const void *ta, const void *tb, const void *tc_ql, const void *tt_4m, const void *tt_4p);
+
+/*
+ * The output spectrum FL2ND of OUTBLOCK with LSECONDORDER = T and the parameters that read it (outblock.F90:168-263, 350-359) for rows
+ * [kijs,kijl): the pipeline of ecwam_hip_outbs_absolute with CAL_SECOND_ORDER_SPEC(FL2ND, WAVNUM, DEPTH, SIG)
+ * (cal_second_order_spec.F90:91-193, secspom.F90:127-288) between INTPOL and the ice noise reshaping:
+ *   FKMEAN of the spectrum after INTPOL (EMEAN, AKMEAN); the depth index JD = NINT(LOG(MAX(1/AKMEAN, DEPTH)/DEPTHA)/LOG(DEPTHD)) + 1 within
+ *   1 .. NDEPTH; thinning to NANGH x NFREH and the f**-5 extension to NMAX; SECSPOM's double sum with the tables of
+ *   ecwam_hip_set_second_order, every bin in the reference's order of additions (no atomics: results do not depend on scheduling); the energy
+ *   conserving interpolation back to NANG x NFRE, switched off where EMEAN > 0.6**2/16 DEPTH**2, with F = MAX(MIN(1E-6, F), F + SIG DELF).
+ * Inputs as ecwam_hip_outbs_absolute, except: wvprpt is always needed (FKMEAN reads WAVNUM); depth: device reals [>= kijl], DEPTH of the
+ * point; sig: +1 adds the correction (what OUTBLOCK does), -1 removes it.  out[npts][8] and fl2nd as ecwam_hip_outbs_absolute; the stages the
+ * two calls share give the same bits, so with all-zero coefficient tables the results are equal bit for bit.
+ * Refused with a reason: no tables set, NANG not 48 / 36 / 24 / 12, fl2nd == fl1.  The call keeps a work space of
+ * NANGH (NMAX + NFREH) reals + 1 int per point on the context, grown on demand (a synchronising allocation on the first call and when
+ * the range grows).  The work space is one per context: calls of this function on one context must be ordered on one stream (or separated by
+ * a synchronisation); two in flight on different streams would overwrite each other's intermediate spectra.  OUTWNORM statistics of a column: ecwam_hip_outwnorm(out + column, stride = 8).
+ */
+int ecwam_hip_outbs_second_order(ecwam_hip_ctx *ctx, int kijs, int kijl, const void *fl1, const void *wvprpt, const void *depth,
+                                 const void *ucur, const void *vcur, const void *ff, double sig, double zmiss, void *out, void *fl2nd,
+                                 void *stream);
 
 /* NEWWIND forcing hand-over (newwind.F90:126-161): FF <- FF_NEXT members + TAUW cap.  ecwam_hip_newwind takes ICODE_WND = ICODE
  * of the parameters; a coupled host (LWCOU) passes ICODE_CPL through ecwam_hip_newwind_icode (newwind.F90:120-124). */
