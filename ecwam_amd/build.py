@@ -120,7 +120,8 @@ def build(force: bool = False, verbose: bool = False, variant: str = "") -> str:
     link_stamp = hashlib.sha256("".join(open(o + ".stamp").read() for o in objs).encode()).hexdigest()
     if not procs and os.path.exists(lib) and os.path.exists(lib + ".stamp") and open(lib + ".stamp").read().strip() == link_stamp:
         return lib
-    cmd = [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib, *objs]
+    # --no-undefined: a launcher that csrc/launch.h declares and no object defines fails here, not when the library is first loaded
+    cmd = [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-Wl,--no-undefined", "-o", lib, *objs]
     r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     if r.returncode != 0:
         raise RuntimeError(f"link failed:\n{r.stdout}")

@@ -10,7 +10,7 @@
 #include <rccl/rccl.h>   // types and prototypes only: librccl is loaded with dlopen when a communicator is asked for
 
 #include "dev.h"
-#include "implsch_adv_args.h"
+#include "launch.h"
 
 static thread_local std::string g_err;
 static int fail(const std::string& m) {
@@ -22,6 +22,11 @@ static int fail(const std::string& m) {
     hipError_t e_ = (x);                                                                 \
     if (e_ != hipSuccess) return fail(std::string(#x) + ": " + hipGetErrorString(e_));   \
   } while (0)
+// the end of an entry point that launched something: the launch's own error, if any
+static int launched() {
+  HIPCHK(hipGetLastError());
+  return 0;
+}
 
 struct ecwam_hip_ctx {
   int real_bytes;
@@ -78,44 +83,11 @@ struct ecwam_hip_ctx {
   int n_obs = 0;
 };
 
-// launchers implemented in propag.hip / implsch.hip
-template <typename T> void launch_propags2(const void*, const void*, void*, const int*, const int*, const int*, const void*, int, int, int, int, int, int, hipStream_t);
-template <typename T> void launch_ctuw(const void*, int, int, int, double, int, int, const int*, const void*, double, const void*, const void*, const int*, const int*, const int*, void*, void*, const void*, const void*, void*, int*, int, const void*, hipStream_t);
-template <typename T> void launch_ctuwini_only(int, int, const int*, const int*, void*, void*, hipStream_t);
-template <typename T> void launch_propdot(const void*, int, int, int, const int*, const void*, double, const void*, const int*, const int*, const void*, const void*, const void*, const void*, const void*, void*, hipStream_t);
-template <typename T> void launch_curmask(int, int, int, const int*, void*, hipStream_t);
-template <typename T> void launch_propags2_gen(const void*, int, const void*, void*, int, double, const int*, const void*, double, const void*, const void*, const int*, const int*, const int*, const void*, const void*, const void*, const void*, const void*, const void*, const void*, int*, int, int, int, int, int, int, int, const void*, hipStream_t);
-template <typename T> void launch_propags2_otf(const void*, const void*, void*, int, int, double, const int*, const void*, double, const void*, const void*, const int*, const int*, const int*, const void*, const void*, const void*, const void*, const int*, int, int, int, int, int, int, const void*, int, double, int, void*, int, const void*, int, int, hipStream_t);
-template <typename T> void launch_copy_freq_range(const void*, void*, int, int, int, int, int, int, hipStream_t);
-template <typename T> int launch_outbs(const void*, int, int, const void*, double, void*, int, int, hipStream_t);
-template <typename T> int launch_outbs_sepwisw(const void*, int, int, const void*, const void*, const void*, const void*, int, double, void*, int, int,
-                                               hipStream_t);
-template <typename T> int launch_outbs_partition(const void*, int, int, const void*, const void*, const int*, const void*, const void*, double, void*, int,
-                                                  int, hipStream_t);
-template <typename T> int launch_outbs_extremes(const void*, int, int, const void*, const void*, const void*, int, void*, int, int, hipStream_t);
-template <typename T> int launch_outbs_absolute(const void*, const void*, int, int, int, const void*, const void*, const void*, const void*, const void*,
-                                                 double, void*, void*, int, int, hipStream_t);
-template <typename T> int launch_outbs_second_order(const void*, const void*, const void*, const void*, void*, int, int, int, int, const void*, const void*,
-                                                     const void*, const void*, const void*, const void*, double, double, void*, void*, int, int, hipStream_t);
-const char* so_tab_build(const ecwam_hip_params*, const void*, int, int, double, double, int, const int*, const int*, std::vector<unsigned char>&);
-void so_coef_layout(int, int, int, int, const void* const[5], std::vector<unsigned char>&);
-size_t so_work_bytes(int, int, int, int, int);
-size_t intpol_tab_build(const ecwam_hip_params*, const ecwam_hip_tables*, int, std::vector<unsigned char>&);
-template <typename T> void launch_norm(const void*, int, int, double, double*, int, hipStream_t);
-template <typename T> void launch_newwind(const void*, int, void*, const void*, int, hipStream_t);
-template <typename T> void launch_nosource(const void*, int, int, int, void*, void*, int*, hipStream_t);
-template <typename T> void launch_c2p(const void*, void*, int, int, int, int, int, hipStream_t);
-template <typename T> void launch_p2c(const void*, void*, int, int, int, int, int, hipStream_t);
-template <typename T> void launch_pack(const void*, const int*, int, int, void*, hipStream_t);
-template <typename T> void launch_proenv_pack(int, int, const void*, const void*, const void*, const void*, const void*, void*, hipStream_t);
-template <typename T> void launch_proenv_unpack(int, int, const void*, const void*, void*, void*, void*, void*, void*, void*, hipStream_t);
-template <typename T> int launch_implsch4(const void*, int, int, void*, const void*, void*, void*, int*, void*, void*, double*, void*, int, void*, int, int, int, int, int, int, hipStream_t);
-template <typename T> int launch_implsch4x(const void*, int, int, void*, const void*, void*, void*, int*, void*, void*, double*, void*, int, void*, int, int, int, int, int, int, hipStream_t);
-template <typename T> int launch_implsch4r(const void*, int, int, void*, const void*, void*, void*, int*, void*, void*, double*, void*, int, void*, int, int, int, int, int, int, hipStream_t);
-template <typename T> void launch_ctu_prep(const void*, int, int, int, double, double, const int*, const void*, double, const void*, const void*, const void*, const void*, const void*, void*, void*, int*, hipStream_t);
-template <typename T> int launch_implsch4_adv(const void*, int, int, void*, const void*, void*, void*, int*, void*, void*, double*, const Implsch4AdvArgs*, int, int, int, int, int, int, hipStream_t);
-int implsch4_adv_forms(int, int);
-int implsch4_fin_row();
+// f(T()) with T = the working precision of the context, float or double: every launch is written once, as launch_x<decltype(t)>(...)
+template <typename F>
+static auto in_precision(const ecwam_hip_ctx* c, F&& f) {
+  return c->real_bytes == 4 ? f(float()) : f(double());
+}
 
 // Does the fourth kernel generation cover these tables?  It needs the pull-form DIA structure with K1W = K -+ r1, K11W = K1W -+ 1,
 // K2W = K +- r2, K21W = K2W +- 1 (kh = 1 / 2) and saturation weights that depend on the tap only (init_sdiss_ardh.F90:88-94: they
@@ -411,8 +383,7 @@ static void fastwave_copy(ecwam_hip_ctx* c, const void* fl1, int kijs, int kijl,
   const size_t rb = (size_t)c->real_bytes;
   const char* src = (const char*)fl1 + (size_t)kijs * c->NANG * c->NFRE * rb;
   char* dst = (char*)c->fast_g + (size_t)kijs * c->NANG * c->fast_gk * rb;
-  if (c->real_bytes == 4) launch_copy_freq_range<float>(src, dst, kijl - kijs, c->NANG, c->NFRE, 0, c->fast_gk, c->fast_gk, s);
-  else launch_copy_freq_range<double>(src, dst, kijl - kijs, c->NANG, c->NFRE, 0, c->fast_gk, c->fast_gk, s);
+  in_precision(c, [&](auto t) { launch_copy_freq_range<decltype(t)>(src, dst, kijl - kijs, c->NANG, c->NFRE, 0, c->fast_gk, c->fast_gk, s); });
 }
 
 // ---- one member of a FIELD_API-shaped host type <-> its slot of the library's packed per-point rows ---------------------------------
@@ -487,21 +458,17 @@ int ecwam_hip_create(const ecwam_hip_params* p, const ecwam_hip_tables* t, int r
     hipError_t e_ = (x);                                                                           \
     if (e_ != hipSuccess) { if (c->dtab) (void)hipFree(c->dtab); if (c->itab) (void)hipFree(c->itab); delete c; return fail(std::string(#x) + ": " + hipGetErrorString(e_)); } \
   } while (0)
-  if (real_bytes == 4) {
-    std::vector<DevTab<float>> h(1);
-    build_tab<float>(p, t, h.data());
+  const int rc_tab = in_precision(c, [&](auto prec) {
+    using T = decltype(prec);
+    std::vector<DevTab<T>> h(1);
+    build_tab<T>(p, t, h.data());
     if (!h[0].DIA_PULL) { delete c; return fail("ecwam_hip_create: the interaction tables do not have the rotation structure of INISNONLIN (K1W = K -+ r1, K2W = K +- r2, INLCOEF = MC, MC+2, MC+3, MC-4, MC-3; KFRH = 8, MFRSTLW = -3): not supported"); }
-    v4_probe<float>(h[0], c);
-    HIPCHK_CTX(hipMalloc(&c->dtab, sizeof(DevTab<float>)));
-    HIPCHK_CTX(hipMemcpy(c->dtab, h.data(), sizeof(DevTab<float>), hipMemcpyHostToDevice));
-  } else {
-    std::vector<DevTab<double>> h(1);
-    build_tab<double>(p, t, h.data());
-    if (!h[0].DIA_PULL) { delete c; return fail("ecwam_hip_create: the interaction tables do not have the rotation structure of INISNONLIN (K1W = K -+ r1, K2W = K +- r2, INLCOEF = MC, MC+2, MC+3, MC-4, MC-3; KFRH = 8, MFRSTLW = -3): not supported"); }
-    v4_probe<double>(h[0], c);
-    HIPCHK_CTX(hipMalloc(&c->dtab, sizeof(DevTab<double>)));
-    HIPCHK_CTX(hipMemcpy(c->dtab, h.data(), sizeof(DevTab<double>), hipMemcpyHostToDevice));
-  }
+    v4_probe<T>(h[0], c);
+    HIPCHK_CTX(hipMalloc(&c->dtab, sizeof(DevTab<T>)));
+    HIPCHK_CTX(hipMemcpy(c->dtab, h.data(), sizeof(DevTab<T>), hipMemcpyHostToDevice));
+    return 0;
+  });
+  if (rc_tab) return rc_tab;
   if (p->irefra >= 2) {   // INTPOL (ecwam_hip_outbs_absolute): FREQ, DFREQTH, deep-water WAVN and the f**-5 factor of M = 1 .. NFRE_MAX
     std::vector<unsigned char> h;
     const size_t nb = intpol_tab_build(p, t, real_bytes, h);
@@ -546,15 +513,6 @@ int ecwam_hip_destroy(ecwam_hip_ctx* c) {
   return 0;
 }
 
-#define DISPATCH(call_f, call_d) \
-  do {                           \
-    if (c->real_bytes == 4) {    \
-      call_f;                    \
-    } else {                     \
-      call_d;                    \
-    }                            \
-  } while (0)
-
 int ecwam_hip_set_obstructions(ecwam_hip_ctx* c, const void* obs, int n) {
   if (!c) return fail("null context");
   if (n < 0 || (obs && n == 0)) return fail("ecwam_hip_set_obstructions: bad size");
@@ -568,12 +526,9 @@ int ecwam_hip_propags2(ecwam_hip_ctx* c, const void* f1, void* f3, const int* kl
   if (kijl < kijs || nd3s < 1 || nd3e > c->NFRE_RED || nd3e < nd3s - 1) return fail("ecwam_hip_propags2: bad range");
   if (kijl > kijs && (!f1 || !f3 || !klon || !klat || !kcor || !w)) return fail("ecwam_hip_propags2: null pointer");
   if (f1 == f3) return fail("ecwam_hip_propags2: F1 and F3 must not alias");
-  hipStream_t s = (hipStream_t)stream;
   const int N = (c->NANG << 16) | (c->NFRE << 8) | c->NFRE_RED;
-  DISPATCH(launch_propags2<float>(c->dtab, f1, f3, klon, klat, kcor, w, kijs, kijl, nd3s - 1, nd3e, copy_rest, N, s),
-           launch_propags2<double>(c->dtab, f1, f3, klon, klat, kcor, w, kijs, kijl, nd3s - 1, nd3e, copy_rest, N, s));
-  HIPCHK(hipGetLastError());
-  return 0;
+  in_precision(c, [&](auto t) { launch_propags2<decltype(t)>(c->dtab, f1, f3, klon, klat, kcor, w, kijs, kijl, nd3s - 1, nd3e, copy_rest, N, (hipStream_t)stream); });
+  return launched();
 }
 
 int ecwam_hip_ctuw(ecwam_hip_ctx* c, int n, int nland, int ngy, double delpro, int mstart, int mend, const int* kxlt, const void* zdello,
@@ -584,11 +539,9 @@ int ecwam_hip_ctuw(ecwam_hip_ctx* c, int n, int nland, int ngy, double delpro, i
   if (n > 0 && (!kxlt || !zdello || !cosph || !sinph || !klon || !klat || !kcor || !wlat || !wcor || !cgroup_ext || !cosphm1_ext || !cflfail))
     return fail("ecwam_hip_ctuw: null pointer");
   if (c->obs && n > c->n_obs) return fail("ecwam_hip_ctuw: more points than the obstruction table holds");
-  hipStream_t s = (hipStream_t)stream;
-  DISPATCH(launch_ctuw<float>(c->dtab, n, nland, ngy, delpro, mstart - 1, mend, kxlt, zdello, xdella, cosph, sinph, klon, klat, kcor, wlat, wcor, cgroup_ext, cosphm1_ext, w, cflfail, c->NANG, c->obs, s),
-           launch_ctuw<double>(c->dtab, n, nland, ngy, delpro, mstart - 1, mend, kxlt, zdello, xdella, cosph, sinph, klon, klat, kcor, wlat, wcor, cgroup_ext, cosphm1_ext, w, cflfail, c->NANG, c->obs, s));
-  HIPCHK(hipGetLastError());
-  return 0;
+  const AdvGeom g{kxlt, zdello, xdella, cosph, sinph, klon, klat, kcor, wlat, wcor, cgroup_ext, cosphm1_ext, ngy};
+  in_precision(c, [&](auto t) { launch_ctuw<decltype(t)>(c->dtab, n, nland, delpro, mstart - 1, mend, g, w, cflfail, c->NANG, c->obs, (hipStream_t)stream); });
+  return launched();
 }
 
 int ecwam_hip_propags2_otf_split(ecwam_hip_ctx* c, const void* f1, void* f3, int n, int ngy, double delpro, double delpro_lf, int ifrelfmax,
@@ -637,10 +590,12 @@ int ecwam_hip_propags2_otf_fast(ecwam_hip_ctx* c, const void* f1, void* f3, int 
 #ifdef ECWAM_HIP_DIAGNOSTICS
   { const char* e_ = getenv("ECWAM_HIP_OTF_WALK"); if (e_ && atoi(e_) == 0) copy_rest |= 2; }  // plain grid-stride tile walk
 #endif
-  DISPATCH(launch_propags2_otf<float>(c->dtab, f1, f3, n, ngy, delpro, kxlt, zdello, xdella, cosph, sinph, klon, klat, kcor, wlat, wcor, cgroup_ext, cosphm1_ext, order, kijs, kijl, nd3s - 1, nd3e, copy_rest, N, c->obs, ifrelfmax, delpro_lf, in_nfre, gout, gout_nfre, gin, gin_nfre, out_nfre, s),
-           launch_propags2_otf<double>(c->dtab, f1, f3, n, ngy, delpro, kxlt, zdello, xdella, cosph, sinph, klon, klat, kcor, wlat, wcor, cgroup_ext, cosphm1_ext, order, kijs, kijl, nd3s - 1, nd3e, copy_rest, N, c->obs, ifrelfmax, delpro_lf, in_nfre, gout, gout_nfre, gin, gin_nfre, out_nfre, s));
-  HIPCHK(hipGetLastError());
-  return 0;
+  const AdvGeom g{kxlt, zdello, xdella, cosph, sinph, klon, klat, kcor, wlat, wcor, cgroup_ext, cosphm1_ext, ngy};
+  in_precision(c, [&](auto t) {
+    launch_propags2_otf<decltype(t)>(c->dtab, f1, f3, n, delpro, g, order, kijs, kijl, nd3s - 1, nd3e, copy_rest, N, c->obs, ifrelfmax, delpro_lf, in_nfre, gout,
+                                     gout_nfre, gin, gin_nfre, out_nfre, s);
+  });
+  return launched();
 }
 
 int ecwam_hip_propags2_otf(ecwam_hip_ctx* c, const void* f1, void* f3, int n, int ngy, double delpro, const int* kxlt, const void* zdello,
@@ -656,11 +611,8 @@ int ecwam_hip_copy_freq_range(ecwam_hip_ctx* c, const void* src, void* dst, int 
   if (dst_nfre == 0) dst_nfre = c->NFRE;
   if (n < 0 || m_first < 1 || m_last > c->NFRE || m_last < m_first - 1 || m_last > dst_nfre) return fail("ecwam_hip_copy_freq_range: bad range");
   if (n > 0 && (!src || !dst)) return fail("ecwam_hip_copy_freq_range: null pointer");
-  hipStream_t s = (hipStream_t)stream;
-  DISPATCH(launch_copy_freq_range<float>(src, dst, n, c->NANG, c->NFRE, m_first - 1, m_last, dst_nfre, s),
-           launch_copy_freq_range<double>(src, dst, n, c->NANG, c->NFRE, m_first - 1, m_last, dst_nfre, s));
-  HIPCHK(hipGetLastError());
-  return 0;
+  in_precision(c, [&](auto t) { launch_copy_freq_range<decltype(t)>(src, dst, n, c->NANG, c->NFRE, m_first - 1, m_last, dst_nfre, (hipStream_t)stream); });
+  return launched();
 }
 
 int ecwam_hip_propdot(ecwam_hip_ctx* c, int n, int nland, const int* kxlt, const void* zdello, double xdella, const void* cosph,
@@ -670,28 +622,21 @@ int ecwam_hip_propdot(ecwam_hip_ctx* c, int n, int nland, const int* kxlt, const
   if (n < 0) return fail("ecwam_hip_propdot: bad range");
   if (n > 0 && (!kxlt || !zdello || !cosph || !klon || !klat || !wlat || !cosphm1_ext || !depth_ext || !u_ext || !v_ext || !refr))
     return fail("ecwam_hip_propdot: null pointer");
-  hipStream_t s = (hipStream_t)stream;
-  DISPATCH(launch_propdot<float>(c->dtab, n, nland, c->p.irefra, kxlt, zdello, xdella, cosph, klon, klat, wlat, cosphm1_ext, depth_ext, u_ext, v_ext, refr, s),
-           launch_propdot<double>(c->dtab, n, nland, c->p.irefra, kxlt, zdello, xdella, cosph, klon, klat, wlat, cosphm1_ext, depth_ext, u_ext, v_ext, refr, s));
-  HIPCHK(hipGetLastError());
-  return 0;
+  const AdvGeom g{kxlt, zdello, xdella, cosph, nullptr, klon, klat, nullptr, wlat, nullptr, nullptr, cosphm1_ext, 0};      // (what k_propdot reads)
+  in_precision(c, [&](auto t) { launch_propdot<decltype(t)>(c->dtab, n, nland, c->p.irefra, g, depth_ext, u_ext, v_ext, refr, (hipStream_t)stream); });
+  return launched();
 }
 
 // shared argument checks + launch of the general-IREFRA kernel (f1 == NULL: checks only)
-static int propags2_gen_launch(ecwam_hip_ctx* c, const char* who, const void* f1, void* f3, int ngy, double delpro,
-                               const int* kxlt, const void* zdello, double xdella, const void* cosph, const void* sinph,
-                               const int* klon, const int* klat, const int* kcor, const void* wlat, const void* wcor,
-                               const void* cgroup_ext, const void* omosnh2kd_ext, const void* wavnum_ext, const void* cosphm1_ext,
-                               const void* refr, int* cflfail, int slot, int kijs, int kijl, int m0, int m1, int copy_rest,
+static int propags2_gen_launch(ecwam_hip_ctx* c, const char* who, const void* f1, void* f3, double delpro, const AdvGeom& g, const void* omosnh2kd_ext,
+                               const void* wavnum_ext, const void* refr, int* cflfail, int slot, int kijs, int kijl, int m0, int m1, int copy_rest,
                                hipStream_t s) {
-  if (kijl > kijs && (!kxlt || !zdello || !cosph || !sinph || !klon || !klat || !kcor || !wlat || !wcor || !cgroup_ext || !omosnh2kd_ext ||
-                      !wavnum_ext || !cosphm1_ext || !refr))
+  if (kijl > kijs && (!g.kxlt || !g.zdello || !g.cosph || !g.sinph || !g.klon || !g.klat || !g.kcor || !g.wlat || !g.wcor || !g.cgroup_ext ||
+                      !omosnh2kd_ext || !wavnum_ext || !g.cosphm1_ext || !refr))
     return fail((std::string(who) + ": null pointer").c_str());
   const int N = (c->NANG << 16) | (c->NFRE << 8) | c->NFRE_RED;
-  DISPATCH(launch_propags2_gen<float>(c->dtab, c->p.irefra, f1, f3, ngy, delpro, kxlt, zdello, xdella, cosph, sinph, klon, klat, kcor, wlat, wcor, cgroup_ext, omosnh2kd_ext, wavnum_ext, cosphm1_ext, refr, cflfail, slot, kijs, kijl, m0, m1, copy_rest, N, c->obs, s),
-           launch_propags2_gen<double>(c->dtab, c->p.irefra, f1, f3, ngy, delpro, kxlt, zdello, xdella, cosph, sinph, klon, klat, kcor, wlat, wcor, cgroup_ext, omosnh2kd_ext, wavnum_ext, cosphm1_ext, refr, cflfail, slot, kijs, kijl, m0, m1, copy_rest, N, c->obs, s));
-  HIPCHK(hipGetLastError());
-  return 0;
+  in_precision(c, [&](auto t) { launch_propags2_gen<decltype(t)>(c->dtab, c->p.irefra, f1, f3, delpro, g, omosnh2kd_ext, wavnum_ext, refr, cflfail, slot, kijs, kijl, m0, m1, copy_rest, N, c->obs, s); });
+  return launched();
 }
 
 int ecwam_hip_ctuw_refra(ecwam_hip_ctx* c, int n, int nland, int ngy, double delpro, int mstart, int mend, const int* kxlt,
@@ -705,7 +650,7 @@ int ecwam_hip_ctuw_refra(ecwam_hip_ctx* c, int n, int nland, int ngy, double del
   if (n == 0) return 0;
   hipStream_t s = (hipStream_t)stream;
   // CTUWINI (ctuwupdt.F90:204-214; idempotent), then CTUWDRV for this frequency range (ctuwdrv.F90:93-118)
-  DISPATCH(launch_ctuwini_only<float>(n, nland, klat, kcor, wlat, wcor, s), launch_ctuwini_only<double>(n, nland, klat, kcor, wlat, wcor, s));
+  in_precision(c, [&](auto t) { launch_ctuwini_only<decltype(t)>(n, nland, klat, kcor, wlat, wcor, s); });
   const bool cur = c->p.irefra == 2 || c->p.irefra == 3;
   std::vector<int> prev;  // flags of the first range survive the second range's own CTUWDRV
   if (range == 1) {
@@ -714,9 +659,9 @@ int ecwam_hip_ctuw_refra(ecwam_hip_ctx* c, int n, int nland, int ngy, double del
     HIPCHK(hipStreamSynchronize(s));
   }
   HIPCHK(hipMemsetAsync(cflfail, 0, sizeof(int) * (size_t)n, s));
-  DISPATCH(launch_curmask<float>(n, c->NANG, range, nullptr, refr, s), launch_curmask<double>(n, c->NANG, range, nullptr, refr, s));  // CURMASK = 1
-  int rc = propags2_gen_launch(c, "ecwam_hip_ctuw_refra", nullptr, nullptr, ngy, delpro, kxlt, zdello, xdella, cosph, sinph, klon, klat, kcor,
-                               wlat, wcor, cgroup_ext, omosnh2kd_ext, wavnum_ext, cosphm1_ext, refr, cflfail, range, 0, n, mstart - 1, mend, 0, s);
+  in_precision(c, [&](auto t) { launch_curmask<decltype(t)>(n, c->NANG, range, nullptr, refr, s); });  // CURMASK = 1
+  const AdvGeom g{kxlt, zdello, xdella, cosph, sinph, klon, klat, kcor, wlat, wcor, cgroup_ext, cosphm1_ext, ngy};
+  int rc = propags2_gen_launch(c, "ecwam_hip_ctuw_refra", nullptr, nullptr, delpro, g, omosnh2kd_ext, wavnum_ext, refr, cflfail, range, 0, n, mstart - 1, mend, 0, s);
   if (rc) return rc;
   if (cur && llcflcuroff) {
     // second CTUW call: current refraction / frequency shift switched off where the first one failed, flags reset
@@ -726,10 +671,9 @@ int ecwam_hip_ctuw_refra(ecwam_hip_ctx* c, int n, int nland, int ngy, double del
     bool any = false;
     for (int i = 0; i < n && !any; i++) any = h[i] != 0;
     if (any) {
-      DISPATCH(launch_curmask<float>(n, c->NANG, range, cflfail, refr, s), launch_curmask<double>(n, c->NANG, range, cflfail, refr, s));
+      in_precision(c, [&](auto t) { launch_curmask<decltype(t)>(n, c->NANG, range, cflfail, refr, s); });
       HIPCHK(hipMemsetAsync(cflfail, 0, sizeof(int) * (size_t)n, s));
-      rc = propags2_gen_launch(c, "ecwam_hip_ctuw_refra", nullptr, nullptr, ngy, delpro, kxlt, zdello, xdella, cosph, sinph, klon, klat,
-                               kcor, wlat, wcor, cgroup_ext, omosnh2kd_ext, wavnum_ext, cosphm1_ext, refr, cflfail, range, 0, n, mstart - 1, mend, 0, s);
+      rc = propags2_gen_launch(c, "ecwam_hip_ctuw_refra", nullptr, nullptr, delpro, g, omosnh2kd_ext, wavnum_ext, refr, cflfail, range, 0, n, mstart - 1, mend, 0, s);
       if (rc) return rc;
     }
   }
@@ -755,14 +699,33 @@ int ecwam_hip_propags2_refra(ecwam_hip_ctx* c, const void* f1, void* f3, int n, 
   if (kijl > kijs && (!f1 || !f3)) return fail("ecwam_hip_propags2_refra: null pointer");
   if (f1 == f3) return fail("ecwam_hip_propags2_refra: F1 and F3 must not alias");
   if (c->obs && kijl > c->n_obs) return fail("ecwam_hip_propags2_refra: more points than the obstruction table holds");
-  return propags2_gen_launch(c, "ecwam_hip_propags2_refra", f1, f3, ngy, delpro, kxlt, zdello, xdella, cosph, sinph, klon, klat, kcor, wlat,
-                             wcor, cgroup_ext, omosnh2kd_ext, wavnum_ext, cosphm1_ext, refr, nullptr, range, kijs, kijl, nd3s - 1, nd3e,
+  const AdvGeom g{kxlt, zdello, xdella, cosph, sinph, klon, klat, kcor, wlat, wcor, cgroup_ext, cosphm1_ext, ngy};
+  return propags2_gen_launch(c, "ecwam_hip_propags2_refra", f1, f3, delpro, g, omosnh2kd_ext, wavnum_ext, refr, nullptr, range, kijs, kijl, nd3s - 1, nd3e,
                              copy_rest ? 1 : 0, (hipStream_t)stream);
 }
 
+// The build of k_implsch4 (implsch_v4.h) a context runs.  The common builds (implsch4.hip): flag sets A and B (ext: LLGCBZ0, LLNORMAGAM), with
+// or without the sea-ice damping rates that depend on the frequency only (LCIWA1, LCIWA3, LCISCAL).  The alternate builds (implsch4x.hip), on
+// flag set A only: alt = 1 IPHYS 0 (sinput_jan + sdissip_jan; its TAUWSHELTER is 0), alt = 2 ISNONLIN 1 (TRANSF per interaction frequency) --
+// what the reference's registered configurations select.  Everything else runs the RARE builds (implsch4r.hip: LCIWA2, the NEMO ice stress
+// and strain, ISNONLIN 2, ICODE 1 / 2, LWVFLX_SNL = F, ISNONLIN 1 beside flag set B or IPHYS 0, IPHYS 0 beside flag set B).  ecwam_hip_create
+// has refused what no build covers.
+enum class Implsch4Build { common, alternate, rare };
+struct Implsch4Choice { Implsch4Build build; int ext, alt; };
+static Implsch4Choice implsch4_choice(const ecwam_hip_ctx* c) {
+  const int ext = (c->p.llnormagam || c->p.llgcbz0) ? 1 : 0;
+  const bool rare4 = c->p.lciwa2 || c->p.lwnemocouwrs || c->p.lwnemocoustrn || c->p.isnonlin > 1 || c->p.icode != 3 || !c->p.lwvflx_snl;
+  const int alt = (c->p.iphys == 0 ? 1 : 0) | (c->p.isnonlin == 1 ? 2 : 0);
+  if (rare4 || (alt != 0 && (ext || alt == 3))) return {Implsch4Build::rare, ext, alt};
+  return {alt ? Implsch4Build::alternate : Implsch4Build::common, ext, alt};
+}
+// the configurations the one-kernel step covers (implsch4a.hip: the common builds on IPHYS 1, ISNONLIN 0); everything else runs
+// ecwam_hip_propags2_otf + ecwam_hip_implsch
+static bool fused_ok(const ecwam_hip_ctx* c) {
+  return c->implsch_why.empty() && implsch4_choice(c).build == Implsch4Build::common && c->NFRE == 36;      // (the direction count: one of k_implsch4's, checked at create)
+}
 // The tables the one-kernel step takes its CTU scalars from (k_ctu_prep fills them every call): sized with the fin rows, so that a host that
 // called ecwam_hip_implsch_reserve has no allocation in its time loop on this path either.  Contexts without a one-kernel build hold none.
-static bool fused_ok(const ecwam_hip_ctx* c);
 static int adv_reserve(ecwam_hip_ctx* c, int npts) {
   if (!fused_ok(c) || !implsch4_adv_forms(c->NANG, c->real_bytes)) return 0;
   const size_t need = (size_t)(npts > 0 ? npts : 0) * 12 * c->real_bytes;
@@ -775,14 +738,35 @@ static int adv_reserve(ecwam_hip_ctx* c, int npts) {
   if (!c->adv_dir) HIPCHK(hipMalloc(&c->adv_dir, (size_t)(6 * c->NANG + 4) * c->real_bytes + (size_t)4 * c->NANG * sizeof(int)));
   return 0;
 }
-// the configurations that run the RARE builds of k_implsch4 (ecwam_hip_implsch below makes the same choice)
-static bool runs_rare_builds(const ecwam_hip_ctx* c) {
-  const int ext = (c->p.llnormagam || c->p.llgcbz0) ? 1 : 0;
-  const bool rare4 = c->p.lciwa2 || c->p.lwnemocouwrs || c->p.lwnemocoustrn || c->p.isnonlin > 1 || c->p.icode != 3 || !c->p.lwvflx_snl;
-  const int alt = (c->p.iphys == 0 ? 1 : 0) | (c->p.isnonlin == 1 ? 2 : 0);
-  return !(!rare4 && (alt == 0 || (!ext && alt != 3)));
+// grows the context's per-point buffers to npts points.  `s`: the stream of the IMPLSCH call that needs them (the rows are zeroed ON that
+// stream: a hipMemset on the null stream is not ordered against a non-blocking stream -- the caller's kernels could write their rows
+// before the zeroes arrive; found by test_implsch_in_blocks_is_bit_identical in a long test process); the null stream for the set-up call
+static int implsch_reserve_on(ecwam_hip_ctx* c, int npts, hipStream_t s) {
+  HIPCHK(hipSetDevice(c->device));
+  const size_t need = (size_t)(npts > 0 ? npts : 0) * implsch4_fin_row() * c->real_bytes;
+  if (need > c->fin_bytes) {   // hipFree waits for the kernels still reading the old rows
+    if (c->fin) HIPCHK(hipFree(c->fin));
+    c->fin = nullptr; c->fin_bytes = 0;
+    HIPCHK(hipMalloc(&c->fin, need));
+    HIPCHK(hipMemsetAsync(c->fin, 0, need, s));
+    // growth is a stall anyway (hipFree / hipMalloc): wait for the zeroes, so that a call on ANOTHER stream issued right after this one
+    // (which needs no growth itself) cannot have its rows overwritten by a memset still pending here
+    HIPCHK(hipStreamSynchronize(s));
+    c->fin_bytes = need;
+  }
+  // the split kernel pair parks the wind-input coefficient of every bin between its two halves: a double precision context whose
+  // configuration runs the RARE builds (implsch4r.hip: their dp form is the split) -- NOT every double precision context: the rows are a
+  // fourth spectrum-sized array (68 GB at O1280)
+  const bool split = c->real_bytes == 8 && implsch4_choice(c).build == Implsch4Build::rare;
+  const size_t need_wi = split ? (size_t)(npts > 0 ? npts : 0) * c->NANG * c->NFRE * c->real_bytes : 0;
+  if (need_wi > c->wi_bytes) {
+    if (c->wi) HIPCHK(hipFree(c->wi));
+    c->wi = nullptr; c->wi_bytes = 0;
+    HIPCHK(hipMalloc(&c->wi, need_wi));
+    c->wi_bytes = need_wi;
+  }
+  return adv_reserve(c, npts);
 }
-static int implsch_reserve_on(ecwam_hip_ctx* c, int npts, hipStream_t s, bool sync);
 int ecwam_hip_implsch(ecwam_hip_ctx* c, int kijs, int kijl, void* fl1, const void* wvprpt, void* ff, void* intf, int* mij, void* xllws,
                       double* wam2nemo, void* dbg, void* stream) {
   if (!c) return fail("null context");
@@ -792,42 +776,21 @@ int ecwam_hip_implsch(ecwam_hip_ctx* c, int kijs, int kijl, void* fl1, const voi
   if (kijl > kijs && c->p.lwnemocou && !wam2nemo) return fail("ecwam_hip_implsch: LWNEMOCOU needs the WAVE2OCEAN buffer");
   if (!c->p.lwnemocou) wam2nemo = nullptr;
   hipStream_t s = (hipStream_t)stream;
-  int rc = -1;
   if (!c->implsch_why.empty()) return fail("ecwam_hip_implsch: " + c->implsch_why);
   if (dbg) return fail("ecwam_hip_implsch: the per-point debug rows were an output of the retired one-point-per-wavefront kernel: pass NULL");
-  // k_implsch4 (implsch_v4.h).  The common builds: flag sets A and B (LLGCBZ0, LLNORMAGAM), with or without the sea-ice
-  // damping rates that depend on the frequency only (LCIWA1, LCIWA3, LCISCAL), and on flag set A IPHYS 0 or ISNONLIN 1 -- what the
-  // reference's registered configurations select.  Everything else runs its RARE builds (implsch4r.hip: LCIWA2, the NEMO ice stress and
-  // strain, ISNONLIN 2, ICODE 1 / 2, LWVFLX_SNL = F, ISNONLIN 1 beside flag set B or IPHYS 0, IPHYS 0 beside flag set B).  ecwam_hip_create
-  // has refused what no build covers.
-  const int ext = (c->p.llnormagam || c->p.llgcbz0) ? 1 : 0;
-  const bool rare4 = c->p.lciwa2 || c->p.lwnemocouwrs || c->p.lwnemocoustrn || c->p.isnonlin > 1 || c->p.icode != 3 || !c->p.lwvflx_snl;
-  // the alternate physics the registered configurations select, on flag set A only: 1 = IPHYS 0 (sinput_jan + sdissip_jan; its
-  // TAUWSHELTER is 0), 2 = ISNONLIN 1 (TRANSF per interaction frequency)
-  const int alt = (c->p.iphys == 0 ? 1 : 0) | (c->p.isnonlin == 1 ? 2 : 0);
-  const bool common_ok = !rare4 && (alt == 0 || (!ext && alt != 3));      // (= !runs_rare_builds(c))
-  {
-    if (int rc2 = implsch_reserve_on(c, kijl, s, false)) return rc2;   // no-op once the buffer covers kijl
-    if (!common_ok)
-      DISPATCH(rc = launch_implsch4r<float>(c->dtab, kijs, kijl, fl1, wvprpt, ff, intf, mij, xllws, c->fin, wam2nemo, c->fast_g, c->fast_gk, c->wi, c->NANG, c->NFRE, c->v4_r1, c->v4_r2, c->v4_nh, c->p.iphys == 0 ? 1 : 0, s),
-               rc = launch_implsch4r<double>(c->dtab, kijs, kijl, fl1, wvprpt, ff, intf, mij, xllws, c->fin, wam2nemo, c->fast_g, c->fast_gk, c->wi, c->NANG, c->NFRE, c->v4_r1, c->v4_r2, c->v4_nh, c->p.iphys == 0 ? 1 : 0, s));
-    else if (alt)
-      DISPATCH(rc = launch_implsch4x<float>(c->dtab, kijs, kijl, fl1, wvprpt, ff, intf, mij, xllws, c->fin, wam2nemo, c->fast_g, c->fast_gk, c->wi, c->NANG, c->NFRE, c->v4_r1, c->v4_r2, c->v4_nh, alt, s),
-               rc = launch_implsch4x<double>(c->dtab, kijs, kijl, fl1, wvprpt, ff, intf, mij, xllws, c->fin, wam2nemo, c->fast_g, c->fast_gk, c->wi, c->NANG, c->NFRE, c->v4_r1, c->v4_r2, c->v4_nh, alt, s));
-    else
-      DISPATCH(rc = launch_implsch4<float>(c->dtab, kijs, kijl, fl1, wvprpt, ff, intf, mij, xllws, c->fin, wam2nemo, c->fast_g, c->fast_gk, c->wi, c->NANG, c->NFRE, c->v4_r1, c->v4_r2, c->v4_nh, ext, s),
-               rc = launch_implsch4<double>(c->dtab, kijs, kijl, fl1, wvprpt, ff, intf, mij, xllws, c->fin, wam2nemo, c->fast_g, c->fast_gk, c->wi, c->NANG, c->NFRE, c->v4_r1, c->v4_r2, c->v4_nh, ext, s));
-    if (rc == 0) { HIPCHK(hipGetLastError()); c->implsch_last = 4; return 0; }
-  }
+  const Implsch4Choice b = implsch4_choice(c);
+  if (int rc2 = implsch_reserve_on(c, kijl, s)) return rc2;   // no-op once the buffer covers kijl
+  const int rc = in_precision(c, [&](auto t) {
+    using T = decltype(t);
+    const bool rare = b.build == Implsch4Build::rare, alt = b.build == Implsch4Build::alternate;
+    const auto launch = rare ? launch_implsch4r<T> : alt ? launch_implsch4x<T> : launch_implsch4<T>;
+    return launch(c->dtab, kijs, kijl, fl1, wvprpt, ff, intf, mij, xllws, c->fin, wam2nemo, c->fast_g, c->fast_gk, c->wi, c->NANG, c->NFRE, c->v4_r1, c->v4_r2,
+                  c->v4_nh, rare ? (c->p.iphys == 0 ? 1 : 0) : alt ? b.alt : b.ext, s);
+  });
+  if (rc == 0) { HIPCHK(hipGetLastError()); c->implsch_last = 4; return 0; }
   return fail("ecwam_hip_implsch: no build of k_implsch4 covers the configuration (ecwam_hip_create should have refused it)");
 }
 
-// the configurations the one-kernel step covers (implsch4a.hip); everything else runs ecwam_hip_propags2_otf + ecwam_hip_implsch
-static bool fused_ok(const ecwam_hip_ctx* c) {      // (declared above adv_reserve)
-  if (!c->implsch_why.empty()) return false;
-  const bool rare4 = c->p.lciwa2 || c->p.lwnemocouwrs || c->p.lwnemocoustrn || c->p.isnonlin > 1 || c->p.icode != 3 || !c->p.lwvflx_snl;
-  return !rare4 && c->p.iphys == 1 && c->p.isnonlin == 0 && c->NFRE == 36;      // (the direction count: one of k_implsch4's, checked at create)
-}
 // bit 0: the one-kernel step covers the context; bit 1: also with fast-wave sub-steps (gin); bit 2: also with the obstructions of
 // ecwam_hip_set_obstructions -- a caller takes the one-kernel step when the bits of what it needs are set
 int ecwam_hip_propags2_implsch_supported(ecwam_hip_ctx* c) { return c && fused_ok(c) ? implsch4_adv_forms(c->NANG, c->real_bytes) : 0; }
@@ -858,22 +821,23 @@ int ecwam_hip_propags2_implsch(ecwam_hip_ctx* c, const void* f1, void* f3, int n
   HIPCHK(hipSetDevice(c->device));
   hipStream_t s = (hipStream_t)stream;
   if (kijl == kijs) return 0;
-  if (int rc2 = implsch_reserve_on(c, kijl, s, false)) return rc2;      // (also the tables of the weights: adv_reserve)
+  if (int rc2 = implsch_reserve_on(c, kijl, s)) return rc2;      // (also the tables of the weights: adv_reserve)
   const size_t dir_reals = (size_t)(6 * c->NANG + 4);      // [NANG][4], CMTODEG (+ 3 pad), [NANG][2] for the fast waves' time step
   int* dirI = reinterpret_cast<int*>(reinterpret_cast<char*>(c->adv_dir) + dir_reals * c->real_bytes);
   const double dlf = gin ? delpro_lf : 0.0;
-  DISPATCH(launch_ctu_prep<float>(c->dtab, kijs, kijl, ngy, delpro, dlf, kxlt, zdello, xdella, cosph, sinph, wlat, wcor, cosphm1_ext, c->adv_pt, c->adv_dir, dirI, s),
-           launch_ctu_prep<double>(c->dtab, kijs, kijl, ngy, delpro, dlf, kxlt, zdello, xdella, cosph, sinph, wlat, wcor, cosphm1_ext, c->adv_pt, c->adv_dir, dirI, s));
+  const AdvGeom g{kxlt, zdello, xdella, cosph, sinph, klon, klat, kcor, wlat, wcor, cgroup_ext, cosphm1_ext, ngy};
+  in_precision(c, [&](auto t) { launch_ctu_prep<decltype(t)>(c->dtab, kijs, kijl, delpro, dlf, g, c->adv_pt, c->adv_dir, dirI, s); });
   Implsch4AdvArgs a;
   a.f_in = f1; a.klon = klon; a.klat = klat; a.kcor = kcor; a.cg = cgroup_ext; a.pt = c->adv_pt; a.dirT = c->adv_dir; a.dirI = dirI;
   a.xdella = xdella; a.delpro = delpro; a.m0 = nd3s - 1; a.m1 = nd3e;
   a.gin = gin; a.delpro_lf = dlf; a.gin_k = gin ? gin_nfre : 0; a.mlf = gin ? ifrelfmax : 0;
   a.obs = c->obs;      // ecwam_hip_set_obstructions (LSUBGRID)
   a.gfast = c->fast_g; a.gfast_k = c->fast_g ? c->fast_gk : 0;      // ecwam_hip_set_fastwave_copy, as for ecwam_hip_implsch
-  const int ext = (c->p.llnormagam || c->p.llgcbz0) ? 1 : 0;
-  int rc = -1;
-  DISPATCH(rc = launch_implsch4_adv<float>(c->dtab, kijs, kijl, f3, wvprpt, ff, intf, mij, xllws, c->fin, wam2nemo, &a, c->NANG, c->NFRE, c->v4_r1, c->v4_r2, c->v4_nh, ext, s),
-           rc = launch_implsch4_adv<double>(c->dtab, kijs, kijl, f3, wvprpt, ff, intf, mij, xllws, c->fin, wam2nemo, &a, c->NANG, c->NFRE, c->v4_r1, c->v4_r2, c->v4_nh, ext, s));
+  const int ext = implsch4_choice(c).ext;
+  const int rc = in_precision(c, [&](auto t) {
+    return launch_implsch4_adv<decltype(t)>(c->dtab, kijs, kijl, f3, wvprpt, ff, intf, mij, xllws, c->fin, wam2nemo, &a, c->NANG, c->NFRE, c->v4_r1, c->v4_r2,
+                                            c->v4_nh, ext, s);
+  });
   if (rc != 0) return fail("ecwam_hip_propags2_implsch: no one-kernel build covers the configuration (the strict build of the weights has neither the fast-wave nor the obstruction form)");
   HIPCHK(hipGetLastError());
   c->implsch_last = 4;
@@ -888,40 +852,9 @@ int ecwam_hip_set_fastwave_copy(ecwam_hip_ctx* c, void* g, int g_nfre) {
   return 0;
 }
 
-// grows the context's per-point buffers to npts points.  `s`: the stream of the IMPLSCH call that needs them (the rows are zeroed ON that
-// stream: a hipMemset on the null stream is not ordered against a non-blocking stream -- the caller's kernels could write their rows
-// before the zeroes arrive; found by test_implsch_in_blocks_is_bit_identical in a long test process), or sync = true for the set-up call
-static int implsch_reserve_on(ecwam_hip_ctx* c, int npts, hipStream_t s, bool sync) {
-  HIPCHK(hipSetDevice(c->device));
-  const size_t need = (size_t)(npts > 0 ? npts : 0) * implsch4_fin_row() * c->real_bytes;
-  if (need > c->fin_bytes) {   // hipFree waits for the kernels still reading the old rows
-    if (c->fin) HIPCHK(hipFree(c->fin));
-    c->fin = nullptr; c->fin_bytes = 0;
-    HIPCHK(hipMalloc(&c->fin, need));
-    HIPCHK(hipMemsetAsync(c->fin, 0, need, s));
-    // growth is a stall anyway (hipFree / hipMalloc): wait for the zeroes, so that a call on ANOTHER stream issued right after this one
-    // (which needs no growth itself) cannot have its rows overwritten by a memset still pending here
-    HIPCHK(hipStreamSynchronize(s));
-    (void)sync;
-    c->fin_bytes = need;
-  }
-  // the split kernel pair parks the wind-input coefficient of every bin between its two halves: a double precision context whose
-  // configuration runs the RARE builds (implsch4r.hip: their dp form is the split) -- NOT every double precision context: the rows are a
-  // fourth spectrum-sized array (68 GB at O1280)
-  const bool split = c->real_bytes == 8 && runs_rare_builds(c);
-  const size_t need_wi = split ? (size_t)(npts > 0 ? npts : 0) * c->NANG * c->NFRE * c->real_bytes : 0;
-  if (need_wi > c->wi_bytes) {
-    if (c->wi) HIPCHK(hipFree(c->wi));
-    c->wi = nullptr; c->wi_bytes = 0;
-    HIPCHK(hipMalloc(&c->wi, need_wi));
-    c->wi_bytes = need_wi;
-  }
-  return adv_reserve(c, npts);
-}
-
 int ecwam_hip_implsch_reserve(ecwam_hip_ctx* c, int npts) {
   if (!c) return fail("ecwam_hip_implsch_reserve: null context");
-  return implsch_reserve_on(c, npts, nullptr, true);
+  return implsch_reserve_on(c, npts, nullptr);
 }
 
 int ecwam_hip_implsch_generation_used(ecwam_hip_ctx* c) { return c ? c->implsch_last : 0; }
@@ -930,70 +863,53 @@ int ecwam_hip_implsch_generation_used(ecwam_hip_ctx* c) { return c ? c->implsch_
 // kernel that want to run on exactly the tables the product runs on (tests/csrc/implsch_v2.hip).
 const void* ecwam_hip_device_tables(ecwam_hip_ctx* c) { return c ? c->dtab : nullptr; }
 
-int ecwam_hip_outbs(ecwam_hip_ctx* c, int kijs, int kijl, const void* fl1, double zmiss, void* out, void* stream) {
+// the head and the tail the ecwam_hip_outbs* entry points share: null context, then the range; the launcher's refusal, then the launch's error
+static int outbs_head(const ecwam_hip_ctx* c, int kijs, int kijl, const char* bad_range) {
   if (!c) return fail("null context");
-  if (kijl < kijs || kijs < 0) return fail("ecwam_hip_outbs: bad range");
-  if (kijl > kijs && (!fl1 || !out)) return fail("ecwam_hip_outbs: null pointer");
-  hipStream_t s = (hipStream_t)stream;
-  int rc;
-  DISPATCH(rc = launch_outbs<float>(c->dtab, kijs, kijl, fl1, zmiss, out, c->NANG, c->NFRE, s),
-           rc = launch_outbs<double>(c->dtab, kijs, kijl, fl1, zmiss, out, c->NANG, c->NFRE, s));
-  if (rc) return fail("ecwam_hip_outbs: unsupported spectral size");
-  HIPCHK(hipGetLastError());
+  if (kijl < kijs || kijs < 0) return fail(bad_range);
   return 0;
+}
+static int outbs_tail(int rc, const char* unsupported) { return rc ? fail(unsupported) : launched(); }
+
+int ecwam_hip_outbs(ecwam_hip_ctx* c, int kijs, int kijl, const void* fl1, double zmiss, void* out, void* stream) {
+  if (outbs_head(c, kijs, kijl, "ecwam_hip_outbs: bad range")) return 1;
+  if (kijl > kijs && (!fl1 || !out)) return fail("ecwam_hip_outbs: null pointer");
+  const int rc = in_precision(c, [&](auto t) { return launch_outbs<decltype(t)>(c->dtab, kijs, kijl, fl1, zmiss, out, c->NANG, c->NFRE, (hipStream_t)stream); });
+  return outbs_tail(rc, "ecwam_hip_outbs: unsupported spectral size");
 }
 
 int ecwam_hip_outbs_sepwisw(ecwam_hip_ctx* c, int kijs, int kijl, const void* fl1, const void* xllws, const void* wvprpt, const void* ff, int flags,
                             double zmiss, void* out, void* stream) {
-  if (!c) return fail("null context");
-  if (kijl < kijs || kijs < 0) return fail("ecwam_hip_outbs_sepwisw: bad range");
+  if (outbs_head(c, kijs, kijl, "ecwam_hip_outbs_sepwisw: bad range")) return 1;
   if (kijl > kijs && (!fl1 || !xllws || !wvprpt || !ff || !out)) return fail("ecwam_hip_outbs_sepwisw: null pointer");
   if (flags & ~1) return fail("ecwam_hip_outbs_sepwisw: unknown flags");
-  hipStream_t s = (hipStream_t)stream;
-  int rc;
-  DISPATCH(rc = launch_outbs_sepwisw<float>(c->dtab, kijs, kijl, fl1, xllws, wvprpt, ff, flags, zmiss, out, c->NANG, c->NFRE, s),
-           rc = launch_outbs_sepwisw<double>(c->dtab, kijs, kijl, fl1, xllws, wvprpt, ff, flags, zmiss, out, c->NANG, c->NFRE, s));
-  if (rc) return fail("ecwam_hip_outbs_sepwisw: unsupported spectral size");
-  HIPCHK(hipGetLastError());
-  return 0;
+  const int rc = in_precision(c, [&](auto t) { return launch_outbs_sepwisw<decltype(t)>(c->dtab, kijs, kijl, fl1, xllws, wvprpt, ff, flags, zmiss, out, c->NANG, c->NFRE, (hipStream_t)stream); });
+  return outbs_tail(rc, "ecwam_hip_outbs_sepwisw: unsupported spectral size");
 }
 
 int ecwam_hip_outbs_partition(ecwam_hip_ctx* c, int kijs, int kijl, const void* fl1, const void* xllws, const int* mij, const void* wvprpt,
                               const void* ff, int flags, double zmiss, void* out, void* stream) {
-  if (!c) return fail("null context");
-  if (kijl < kijs || kijs < 0) return fail("ecwam_hip_outbs_partition: bad range");
+  if (outbs_head(c, kijs, kijl, "ecwam_hip_outbs_partition: bad range")) return 1;
   if (kijl > kijs && (!fl1 || !xllws || !mij || !wvprpt || !ff || !out)) return fail("ecwam_hip_outbs_partition: null pointer");
   if (flags & 1)
     return fail("ecwam_hip_outbs_partition: CLDOMAIN = 's' (flags bit 0) is not supported: SEP3TR would read an FSEA that SEPWISW has not computed");
   if (flags) return fail("ecwam_hip_outbs_partition: unknown flags");
-  hipStream_t s = (hipStream_t)stream;
-  int rc;
-  DISPATCH(rc = launch_outbs_partition<float>(c->dtab, kijs, kijl, fl1, xllws, mij, wvprpt, ff, zmiss, out, c->NANG, c->NFRE, s),
-           rc = launch_outbs_partition<double>(c->dtab, kijs, kijl, fl1, xllws, mij, wvprpt, ff, zmiss, out, c->NANG, c->NFRE, s));
-  if (rc) return fail("ecwam_hip_outbs_partition: unsupported spectral size");
-  HIPCHK(hipGetLastError());
-  return 0;
+  const int rc = in_precision(c, [&](auto t) { return launch_outbs_partition<decltype(t)>(c->dtab, kijs, kijl, fl1, xllws, mij, wvprpt, ff, zmiss, out, c->NANG, c->NFRE, (hipStream_t)stream); });
+  return outbs_tail(rc, "ecwam_hip_outbs_partition: unsupported spectral size");
 }
 
 int ecwam_hip_outbs_extremes(ecwam_hip_ctx* c, int kijs, int kijl, const void* fl1, const void* wvprpt, const void* ff, int flags, void* out,
                              void* stream) {
-  if (!c) return fail("null context");
-  if (kijl < kijs || kijs < 0) return fail("ecwam_hip_outbs_extremes: bad range");
+  if (outbs_head(c, kijs, kijl, "ecwam_hip_outbs_extremes: bad range")) return 1;
   if (kijl > kijs && (!fl1 || !wvprpt || !ff || !out)) return fail("ecwam_hip_outbs_extremes: null pointer");
   if (flags & ~1) return fail("ecwam_hip_outbs_extremes: unknown flags");
-  hipStream_t s = (hipStream_t)stream;
-  int rc;
-  DISPATCH(rc = launch_outbs_extremes<float>(c->dtab, kijs, kijl, fl1, wvprpt, ff, flags, out, c->NANG, c->NFRE, s),
-           rc = launch_outbs_extremes<double>(c->dtab, kijs, kijl, fl1, wvprpt, ff, flags, out, c->NANG, c->NFRE, s));
-  if (rc) return fail("ecwam_hip_outbs_extremes: unsupported spectral size");
-  HIPCHK(hipGetLastError());
-  return 0;
+  const int rc = in_precision(c, [&](auto t) { return launch_outbs_extremes<decltype(t)>(c->dtab, kijs, kijl, fl1, wvprpt, ff, flags, out, c->NANG, c->NFRE, (hipStream_t)stream); });
+  return outbs_tail(rc, "ecwam_hip_outbs_extremes: unsupported spectral size");
 }
 
 int ecwam_hip_outbs_absolute(ecwam_hip_ctx* c, int kijs, int kijl, const void* fl1, const void* wvprpt, const void* ucur, const void* vcur,
                              const void* ff, int flags, double zmiss, void* out, void* fl2nd, void* stream) {
-  if (!c) return fail("null context");
-  if (kijl < kijs || kijs < 0) return fail("ecwam_hip_outbs_absolute: bad range");
+  if (outbs_head(c, kijs, kijl, "ecwam_hip_outbs_absolute: bad range")) return 1;
   if (flags) return fail("ecwam_hip_outbs_absolute: unknown flags");
   const bool intpol = c->p.irefra >= 2, ice = c->p.licerun && !c->p.lmaskice;
   if (kijl > kijs && (!fl1 || !out)) return fail("ecwam_hip_outbs_absolute: null pointer");
@@ -1003,12 +919,8 @@ int ecwam_hip_outbs_absolute(ecwam_hip_ctx* c, int kijs, int kijl, const void* f
   if (intpol && !c->itab) return fail("ecwam_hip_outbs_absolute: NFRE_MAX of INTPOL exceeds the library's table");
   hipStream_t s = (hipStream_t)stream;
   const int mode = (intpol ? 1 : 0) | (ice ? 2 : 0);
-  int rc;
-  DISPATCH(rc = launch_outbs_absolute<float>(c->dtab, c->itab, kijs, kijl, mode, fl1, wvprpt, ucur, vcur, ff, zmiss, out, fl2nd, c->NANG, c->NFRE, s),
-           rc = launch_outbs_absolute<double>(c->dtab, c->itab, kijs, kijl, mode, fl1, wvprpt, ucur, vcur, ff, zmiss, out, fl2nd, c->NANG, c->NFRE, s));
-  if (rc) return fail("ecwam_hip_outbs_absolute: unsupported spectral size");
-  HIPCHK(hipGetLastError());
-  return 0;
+  const int rc = in_precision(c, [&](auto t) { return launch_outbs_absolute<decltype(t)>(c->dtab, c->itab, kijs, kijl, mode, fl1, wvprpt, ucur, vcur, ff, zmiss, out, fl2nd, c->NANG, c->NFRE, s); });
+  return outbs_tail(rc, "ecwam_hip_outbs_absolute: unsupported spectral size");
 }
 
 int ecwam_hip_set_second_order(ecwam_hip_ctx* c, int ndepth, double deptha, double depthd, int nmax, const int* im_p, const int* im_m, const void* ta,
@@ -1037,8 +949,7 @@ int ecwam_hip_set_second_order(ecwam_hip_ctx* c, int ndepth, double deptha, doub
 
 int ecwam_hip_outbs_second_order(ecwam_hip_ctx* c, int kijs, int kijl, const void* fl1, const void* wvprpt, const void* depth, const void* ucur,
                                  const void* vcur, const void* ff, double sig, double zmiss, void* out, void* fl2nd, void* stream) {
-  if (!c) return fail("null context");
-  if (kijl < kijs || kijs < 0) return fail("ecwam_hip_outbs_second_order: bad range");
+  if (outbs_head(c, kijs, kijl, "ecwam_hip_outbs_second_order: bad range")) return 1;
   if (!c->so_tab || !c->so_coef) return fail("ecwam_hip_outbs_second_order: the second-order tables are not set (ecwam_hip_set_second_order)");
   const bool intpol = c->p.irefra >= 2, ice = c->p.licerun && !c->p.lmaskice;
   if (kijl > kijs && (!fl1 || !out || !wvprpt || !depth)) return fail("ecwam_hip_outbs_second_order: null pointer (fl1, wvprpt, depth and out are needed)");
@@ -1059,14 +970,11 @@ int ecwam_hip_outbs_second_order(ecwam_hip_ctx* c, int kijs, int kijl, const voi
     c->so_work_bytes = need;
   }
   const int mode = (intpol ? 1 : 0) | (ice ? 2 : 0);
-  int rc;
-  DISPATCH(rc = launch_outbs_second_order<float>(c->dtab, c->itab, c->so_tab, c->so_coef, c->so_work, c->so_nmax, kijs, kijl, mode, fl1, wvprpt, depth, ucur,
-                                                 vcur, ff, sig, zmiss, out, fl2nd, c->NANG, c->NFRE, s),
-           rc = launch_outbs_second_order<double>(c->dtab, c->itab, c->so_tab, c->so_coef, c->so_work, c->so_nmax, kijs, kijl, mode, fl1, wvprpt, depth, ucur,
-                                                  vcur, ff, sig, zmiss, out, fl2nd, c->NANG, c->NFRE, s));
-  if (rc) return fail("ecwam_hip_outbs_second_order: unsupported spectral size (NANG must be 48, 36, 24 or 12)");
-  HIPCHK(hipGetLastError());
-  return 0;
+  const int rc = in_precision(c, [&](auto t) {
+    return launch_outbs_second_order<decltype(t)>(c->dtab, c->itab, c->so_tab, c->so_coef, c->so_work, c->so_nmax, kijs, kijl, mode, fl1, wvprpt, depth, ucur, vcur,
+                                                  ff, sig, zmiss, out, fl2nd, c->NANG, c->NFRE, s);
+  });
+  return outbs_tail(rc, "ecwam_hip_outbs_second_order: unsupported spectral size (NANG must be 48, 36, 24 or 12)");
 }
 
 int ecwam_hip_outwnorm(ecwam_hip_ctx* c, const void* field, int stride, int n, double zmiss, double* result, void* stream) {
@@ -1077,7 +985,7 @@ int ecwam_hip_outwnorm(ecwam_hip_ctx* c, const void* field, int stride, int n, d
   HIPCHK(hipSetDevice(c->device));
   if (!c->norm_scratch) HIPCHK(hipMalloc(&c->norm_scratch, (size_t)(4 + 4 * nb) * sizeof(double)));
   double* scratch = c->norm_scratch;
-  DISPATCH(launch_norm<float>(field, stride, n, zmiss, scratch, nb, s), launch_norm<double>(field, stride, n, zmiss, scratch, nb, s));
+  in_precision(c, [&](auto t) { launch_norm<decltype(t)>(field, stride, n, zmiss, scratch, nb, s); });
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpyAsync(result, scratch, 4 * sizeof(double), hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
@@ -1088,10 +996,8 @@ int ecwam_hip_newwind_icode(ecwam_hip_ctx* c, int n, void* ff, const void* ff_ne
   if (!c) return fail("null context");
   if (n > 0 && (!ff || !ff_next)) return fail("ecwam_hip_newwind: null pointer");
   if (icode_wnd < 1 || icode_wnd > 3) return fail("ecwam_hip_newwind: ICODE_WND must be 1, 2 or 3");
-  hipStream_t s = (hipStream_t)stream;
-  DISPATCH(launch_newwind<float>(c->dtab, n, ff, ff_next, icode_wnd, s), launch_newwind<double>(c->dtab, n, ff, ff_next, icode_wnd, s));
-  HIPCHK(hipGetLastError());
-  return 0;
+  in_precision(c, [&](auto t) { launch_newwind<decltype(t)>(c->dtab, n, ff, ff_next, icode_wnd, (hipStream_t)stream); });
+  return launched();
 }
 int ecwam_hip_newwind(ecwam_hip_ctx* c, int n, void* ff, const void* ff_next, void* stream) {
   if (!c) return fail("null context");
@@ -1103,8 +1009,7 @@ int ecwam_hip_nosource(ecwam_hip_ctx* c, int kijs, int kijl, void* fl1, int* mij
   if (kijs < 0 || kijl < kijs) return fail("ecwam_hip_nosource: bad range");
   if (kijl > kijs && (!mij || !xllws)) return fail("ecwam_hip_nosource: null pointer");
   hipStream_t s = (hipStream_t)stream;
-  DISPATCH(launch_nosource<float>(c->dtab, kijs, kijl, c->NANG * c->NFRE, fl1, xllws, mij, s),
-           launch_nosource<double>(c->dtab, kijs, kijl, c->NANG * c->NFRE, fl1, xllws, mij, s));
+  in_precision(c, [&](auto t) { launch_nosource<decltype(t)>(c->dtab, kijs, kijl, c->NANG * c->NFRE, fl1, xllws, mij, s); });
   HIPCHK(hipGetLastError());
   if (c->fast_g && fl1 && kijl > kijs) { fastwave_copy(c, fl1, kijs, kijl, s); HIPCHK(hipGetLastError()); }
   return 0;
@@ -1125,19 +1030,15 @@ int ecwam_hip_host_unregister(ecwam_hip_ctx* c, void* host) {
 int ecwam_hip_chunks_to_points(ecwam_hip_ctx* c, const void* chunked, void* points, int nproma, int nchnk, int npts, int n2, int n3, void* stream) {
   if (!c) return fail("null context");
   if (nproma < 1 || nchnk < 0 || npts > nproma * nchnk || n2 < 1 || n3 < 1) return fail("ecwam_hip_chunks_to_points: bad shape");
-  hipStream_t s = (hipStream_t)stream;
-  DISPATCH(launch_c2p<float>(chunked, points, nproma, nchnk, npts, n2, n3, s), launch_c2p<double>(chunked, points, nproma, nchnk, npts, n2, n3, s));
-  HIPCHK(hipGetLastError());
-  return 0;
+  in_precision(c, [&](auto t) { launch_c2p<decltype(t)>(chunked, points, nproma, nchnk, npts, n2, n3, (hipStream_t)stream); });
+  return launched();
 }
 
 int ecwam_hip_points_to_chunks(ecwam_hip_ctx* c, const void* points, void* chunked, int nproma, int nchnk, int npts, int n2, int n3, void* stream) {
   if (!c) return fail("null context");
   if (nproma < 1 || nchnk < 0 || npts > nproma * nchnk || npts <= nproma * (nchnk - 1) || n2 < 1 || n3 < 1) return fail("ecwam_hip_points_to_chunks: bad shape");
-  hipStream_t s = (hipStream_t)stream;
-  DISPATCH(launch_p2c<float>(points, chunked, nproma, nchnk, npts, n2, n3, s), launch_p2c<double>(points, chunked, nproma, nchnk, npts, n2, n3, s));
-  HIPCHK(hipGetLastError());
-  return 0;
+  in_precision(c, [&](auto t) { launch_p2c<decltype(t)>(points, chunked, nproma, nchnk, npts, n2, n3, (hipStream_t)stream); });
+  return launched();
 }
 
 static int member_args(const char* who, int nproma, int nchnk, int npts, int nm, long long row_stride, long long row_off, int elem_bytes,
@@ -1161,8 +1062,7 @@ int ecwam_hip_member_scatter(ecwam_hip_ctx* c, const void* chunked, void* rows, 
     hipLaunchKernelGGL(k_member_scatter<unsigned int>, dim3(nb), dim3(256), 0, s, (const unsigned int*)chunked, (unsigned int*)rows, nproma, npts, nm, row_stride, row_off);
   else
     hipLaunchKernelGGL(k_member_scatter<unsigned long long>, dim3(nb), dim3(256), 0, s, (const unsigned long long*)chunked, (unsigned long long*)rows, nproma, npts, nm, row_stride, row_off);
-  HIPCHK(hipGetLastError());
-  return 0;
+  return launched();
 }
 
 int ecwam_hip_member_gather(ecwam_hip_ctx* c, const void* rows, void* chunked, int nproma, int nchnk, int npts, int nm, long long row_stride,
@@ -1177,18 +1077,15 @@ int ecwam_hip_member_gather(ecwam_hip_ctx* c, const void* rows, void* chunked, i
     hipLaunchKernelGGL(k_member_gather<unsigned int>, dim3(nb), dim3(256), 0, s, (const unsigned int*)rows, (unsigned int*)chunked, nproma, nchnk, npts, nm, row_stride, row_off);
   else
     hipLaunchKernelGGL(k_member_gather<unsigned long long>, dim3(nb), dim3(256), 0, s, (const unsigned long long*)rows, (unsigned long long*)chunked, nproma, nchnk, npts, nm, row_stride, row_off);
-  HIPCHK(hipGetLastError());
-  return 0;
+  return launched();
 }
 
 int ecwam_hip_pack_rows(ecwam_hip_ctx* c, const void* fl, const int* idx, int n, void* buf, void* stream) {
   if (!c) return fail("null context");
   if (n > 0 && (!fl || !idx || !buf)) return fail("ecwam_hip_pack_rows: null pointer");
-  hipStream_t s = (hipStream_t)stream;
   const int rowlen = c->NANG * c->NFRE;
-  DISPATCH(launch_pack<float>(fl, idx, n, rowlen, buf, s), launch_pack<double>(fl, idx, n, rowlen, buf, s));
-  HIPCHK(hipGetLastError());
-  return 0;
+  in_precision(c, [&](auto t) { launch_pack<decltype(t)>(fl, idx, n, rowlen, buf, (hipStream_t)stream); });
+  return launched();
 }
 
 int ecwam_hip_unpack_rows(ecwam_hip_ctx* c, const void* buf, int n, void* fl, int dst0, void* stream) {
@@ -1233,10 +1130,8 @@ int ecwam_hip_proenvhalo_pack(ecwam_hip_ctx* c, int n, const void* wvprpt, const
                               void* buffer_ext, void* stream) {
   if (!c) return fail("null context");
   if (n < 0 || (n > 0 && (!wvprpt || !omosnh2kd || !depth || !ucur || !vcur || !buffer_ext))) return fail("ecwam_hip_proenvhalo_pack: bad arguments");
-  DISPATCH(launch_proenv_pack<float>(n, c->NFRE, wvprpt, omosnh2kd, depth, ucur, vcur, buffer_ext, (hipStream_t)stream),
-           launch_proenv_pack<double>(n, c->NFRE, wvprpt, omosnh2kd, depth, ucur, vcur, buffer_ext, (hipStream_t)stream));
-  HIPCHK(hipGetLastError());
-  return 0;
+  in_precision(c, [&](auto t) { launch_proenv_pack<decltype(t)>(n, c->NFRE, wvprpt, omosnh2kd, depth, ucur, vcur, buffer_ext, (hipStream_t)stream); });
+  return launched();
 }
 
 int ecwam_hip_proenvhalo_unpack(ecwam_hip_ctx* c, int nrows, const void* buffer_ext, const void* land, void* wavnum_ext, void* cgroup_ext,
@@ -1244,10 +1139,8 @@ int ecwam_hip_proenvhalo_unpack(ecwam_hip_ctx* c, int nrows, const void* buffer_
   if (!c) return fail("null context");
   if (nrows < 0 || !buffer_ext || !land || !wavnum_ext || !cgroup_ext || !omosnh2kd_ext || !depth_ext || !u_ext || !v_ext)
     return fail("ecwam_hip_proenvhalo_unpack: bad arguments");
-  DISPATCH(launch_proenv_unpack<float>(nrows, c->NFRE, buffer_ext, land, wavnum_ext, cgroup_ext, omosnh2kd_ext, depth_ext, u_ext, v_ext, (hipStream_t)stream),
-           launch_proenv_unpack<double>(nrows, c->NFRE, buffer_ext, land, wavnum_ext, cgroup_ext, omosnh2kd_ext, depth_ext, u_ext, v_ext, (hipStream_t)stream));
-  HIPCHK(hipGetLastError());
-  return 0;
+  in_precision(c, [&](auto t) { launch_proenv_unpack<decltype(t)>(nrows, c->NFRE, buffer_ext, land, wavnum_ext, cgroup_ext, omosnh2kd_ext, depth_ext, u_ext, v_ext, (hipStream_t)stream); });
+  return launched();
 }
 
 int ecwam_hip_halo_counts(ecwam_hip_ctx* c, int* n_send, int* n_recv) {
@@ -1317,8 +1210,7 @@ static int halo_pack(ecwam_hip_ctx* c, ecwam_hip_ctx::HaloSlot* q, const void* f
     q->bytes = need;
   }
   if (c->n_send > 0) {
-    DISPATCH(launch_pack<float>(fl, c->d_send_idx, c->n_send, rowlen, q->buf, s),
-             launch_pack<double>(fl, c->d_send_idx, c->n_send, rowlen, q->buf, s));
+    in_precision(c, [&](auto t) { launch_pack<decltype(t)>(fl, c->d_send_idx, c->n_send, rowlen, q->buf, s); });
     HIPCHK(hipGetLastError());
   }
   return 0;

@@ -4,6 +4,7 @@
 // ISNONLIN = 0, ICODE = 3; NFRE = 36, NANG = 48 / 36 / 24 / 12, single and double precision.  (IPHYS 0 / ISNONLIN 1: implsch4x.hip; every
 // other switch: implsch4r.hip.)
 #include "implsch_v4_launch.h"
+#include "launch.h"
 
 // returns 0 when launched, -1 when no instantiation covers (NANG, r1, r2, nh): ecwam_hip_create refuses those configurations
 template <typename T>

@@ -5,7 +5,7 @@
 // ADV = 5 / 7 the same with the sub-grid obstructions of LSUBGRID (the reference's default on real bathymetry).  Everything else runs the
 // two kernels (ecwam_hip_propags2_otf + ecwam_hip_implsch), which is also the A/B partner: the results are bit-identical.
 #include "implsch_v4_launch.h"
-#include "implsch_adv_args.h"
+#include "launch.h"
 
 // returns 0 when launched, -1 when no ADV build covers the configuration (the caller then runs the two kernels)
 template <typename T>

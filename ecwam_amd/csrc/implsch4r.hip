@@ -4,6 +4,7 @@
 // IPHYS = 0 -- decided at run time inside two builds per direction count: flag sets A and B with IPHYS = 1 (EXT + ENHMC), and IPHYS = 0 on
 // flag set A (JAN + ENHMC).  A translation unit of its own: the builds compile beside those of implsch4.hip / implsch4x.hip.
 #include "implsch_v4_launch.h"
+#include "launch.h"
 
 // jan: 1 = IPHYS 0.  Returns 0 when launched, -1 when no instantiation covers the configuration (ecwam_hip_create refuses those).
 // V4R_PREC selects the precision this object instantiates: 1 = single (implsch4r.o), 2 = double (implsch4rd.o).

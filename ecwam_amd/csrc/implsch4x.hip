@@ -3,6 +3,7 @@
 // interaction frequency), both on flag set A (LLGCBZ0 = F, LLNORMAGAM = F).  A translation unit of its own: the builds compile beside
 // those of implsch4.hip.
 #include "implsch_v4_launch.h"
+#include "launch.h"
 
 // variant: 1 = IPHYS 0, 2 = ISNONLIN 1.  Returns 0 when launched, -1 when no instantiation covers the configuration (ecwam_hip_create refuses those).
 template <typename T>

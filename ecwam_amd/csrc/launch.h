@@ -1,0 +1,83 @@
+// The host launchers of the kernels, and the table builders beside them, that capi.hip calls: declared here once, with their parameter
+// names.  capi.hip includes this file and so does every file that defines one of them; the explicit instantiations at the end of those files
+// spell these signatures, so a definition that drifts from its declaration does not compile.
+#pragma once
+#include <cstddef>
+#include <vector>
+
+#include <hip/hip_runtime.h>
+
+#include "../../include/ecwam_hip.h"
+#include "implsch_adv_args.h"
+
+// The grid geometry the advection kernels form the CTU weights from, in the untyped form and the order of the C interface's arguments
+// (ecwam_hip_ctuw, ecwam_hip_propags2_otf ...).  An entry point that does not have one of them leaves it NULL / 0.
+struct AdvGeom {
+  const int* kxlt;
+  const void* zdello;
+  double xdella;
+  const void *cosph, *sinph;
+  const int *klon, *klat, *kcor;
+  const void *wlat, *wcor;      // read by every kernel but CTUWINI (launch_ctuw), which fills them
+  const void *cgroup_ext, *cosphm1_ext;
+  int ngy;
+};
+
+// ---- propag.hip ----------------------------------------------------------------------------------------------------------------------
+// dims = NANG << 16 | NFRE << 8 | NFRE_RED; [m0, m1) = the advected frequencies, 0-based
+template <typename T> void launch_propags2(const void* tab, const void* f1, void* f3, const int* klon, const int* klat, const int* kcor, const void* w, int kijs, int kijl, int m0, int m1,
+        int copy_rest, int dims, hipStream_t s);
+template <typename T> void launch_ctuw(const void* tab, int n, int nland, double delpro, int m0, int m1, const AdvGeom& g, void* w, int* cflfail, int NANG, const void* obs, hipStream_t s);
+template <typename T> void launch_ctuwini_only(int n, int nland, const int* klat, const int* kcor, void* wlat, void* wcor, hipStream_t s);
+template <typename T> void launch_propdot(const void* tab, int n, int nland, int irefra, const AdvGeom& g, const void* depth, const void* ue, const void* ve, void* refr, hipStream_t s);
+template <typename T> void launch_curmask(int n, int NANG, int slot, const int* cflfail, void* refr, hipStream_t s);
+template <typename T> void launch_propags2_gen(const void* tab, int irefra, const void* f1, void* f3, double delpro, const AdvGeom& g, const void* om, const void* wn, const void* refr,
+        int* cflfail, int slot, int kijs, int kijl, int m0, int m1, int copy_rest, int dims, const void* obs, hipStream_t s);
+template <typename T> void launch_propags2_otf(const void* tab, const void* f1, void* f3, int n_geom, double delpro, const AdvGeom& g, const int* order, int kijs, int kijl, int m0,
+        int m1, int copy_rest, int dims, const void* obs, int mlf, double delpro_lf, int in_k, void* gout, int gout_k, const void* gin, int gin_k, int out_k, hipStream_t s);
+template <typename T> void launch_copy_freq_range(const void* src, void* dst, int n, int NANG, int NFRE, int m0, int m1, int dst_nfre, hipStream_t s);
+template <typename T> void launch_newwind(const void* tab, int n, void* ff, const void* ffn, int icode_wnd, hipStream_t s);
+template <typename T> void launch_ctu_prep(const void* tab, int kijs, int kijl, double delpro, double delpro_lf, const AdvGeom& g, void* pt, void* dirT, int* dirI, hipStream_t s);
+template <typename T> void launch_nosource(const void* tab, int kijs, int kijl, int rowlen, void* fl1, void* xllws, int* mij, hipStream_t s);
+template <typename T> void launch_c2p(const void* ch, void* pt, int nproma, int nchnk, int npts, int n2, int n3, hipStream_t s);
+template <typename T> void launch_p2c(const void* pt, void* ch, int nproma, int nchnk, int npts, int n2, int n3, hipStream_t s);
+template <typename T> void launch_pack(const void* fl, const int* idx, int n, int rowlen, void* buf, hipStream_t s);
+template <typename T> void launch_proenv_pack(int n, int NFRE, const void* wvprpt, const void* om, const void* depth, const void* u, const void* v, void* buf, hipStream_t s);
+template <typename T> void launch_proenv_unpack(int nrows, int NFRE, const void* buf, const void* land, void* wn, void* cg, void* om, void* dep, void* u, void* v, hipStream_t s);
+
+// ---- implsch4.hip, implsch4x.hip, implsch4r.hip, implsch4a.hip: 0 = launched, -1 = no instantiation covers the configuration ------------
+// sel: EXT (flag set B) for launch_implsch4, the variant (1 = IPHYS 0, 2 = ISNONLIN 1) for launch_implsch4x, JAN (IPHYS 0) for launch_implsch4r
+template <typename T> int launch_implsch4(const void* tab, int kijs, int kijl, void* fl1, const void* wvprpt, void* ff, void* intf, int* mij, void* xllws, void* fin, double* w2n,
+        void* gfast, int gk, void* wi, int NANG, int NFRE, int r1, int r2, int nh, int sel, hipStream_t s);
+template <typename T> int launch_implsch4x(const void* tab, int kijs, int kijl, void* fl1, const void* wvprpt, void* ff, void* intf, int* mij, void* xllws, void* fin, double* w2n,
+        void* gfast, int gk, void* wi, int NANG, int NFRE, int r1, int r2, int nh, int sel, hipStream_t s);
+template <typename T> int launch_implsch4r(const void* tab, int kijs, int kijl, void* fl1, const void* wvprpt, void* ff, void* intf, int* mij, void* xllws, void* fin, double* w2n,
+        void* gfast, int gk, void* wi, int NANG, int NFRE, int r1, int r2, int nh, int sel, hipStream_t s);
+template <typename T> int launch_implsch4_adv(const void* tab, int kijs, int kijl, void* fl_out, const void* wvprpt, void* ff, void* intf, int* mij, void* xllws, void* fin, double* w2n,
+        const Implsch4AdvArgs* a, int NANG, int NFRE, int r1, int r2, int nh, int ext, hipStream_t s);
+int implsch4_adv_forms(int NANG, int real_bytes);
+int implsch4_fin_row();
+
+// ---- outbs*.hip: 0 = launched (or nothing to do), 1 = unsupported spectral size -------------------------------------------------------------
+// the spectral sizes of the output kernels: four LDS tiles [NFRE][NANG | 1] within 64 KiB, a direction per lane, a frequency per mask bit
+inline bool outbs_size_ok(int NANG, int NFRE, size_t real_bytes) {
+  return (size_t)4 * NFRE * (NANG | 1) * real_bytes <= 64 * 1024 && NANG <= 64 && NFRE <= 63;
+}
+template <typename T> int launch_outbs(const void* tab, int kijs, int kijl, const void* fl1, double zmiss, void* out, int NANG, int NFRE, hipStream_t s);
+template <typename T> void launch_norm(const void* f, int stride, int n, double zmiss, double* scratch, int nb, hipStream_t s);
+template <typename T> int launch_outbs_sepwisw(const void* tab, int kijs, int kijl, const void* fl1, const void* xllws, const void* wvprpt, const void* ff, int flags, double zmiss,
+        void* out, int NANG, int NFRE, hipStream_t s);
+template <typename T> int launch_outbs_partition(const void* tab, int kijs, int kijl, const void* fl1, const void* xllws, const int* mij, const void* wvprpt, const void* ff, double zmiss,
+        void* out, int NANG, int NFRE, hipStream_t s);
+template <typename T> int launch_outbs_extremes(const void* tab, int kijs, int kijl, const void* fl1, const void* wvprpt, const void* ff, int flags, void* out, int NANG, int NFRE,
+        hipStream_t s);
+template <typename T> int launch_outbs_absolute(const void* tab, const void* itab, int kijs, int kijl, int mode, const void* fl1, const void* wvprpt, const void* ucur, const void* vcur,
+        const void* ff, double zmiss, void* out, void* fl2nd, int NANG, int NFRE, hipStream_t s);
+template <typename T> int launch_outbs_second_order(const void* tab, const void* itab, const void* sotab, const void* coef, void* work, int nmax, int kijs, int kijl, int mode,
+        const void* fl1, const void* wvprpt, const void* depth, const void* ucur, const void* vcur, const void* ff, double sig, double zmiss, void* out, void* fl2nd, int NANG, int NFRE,
+        hipStream_t s);
+size_t intpol_tab_build(const ecwam_hip_params* p, const ecwam_hip_tables* t, int real_bytes, std::vector<unsigned char>& host);
+const char* so_tab_build(const ecwam_hip_params* p, const void* fr, int real_bytes, int ndepth, double deptha, double depthd, int nmax, const int* im_p, const int* im_m,
+        std::vector<unsigned char>& host);
+void so_coef_layout(int real_bytes, int ND, int AH, int NH, const void* const src[5], std::vector<unsigned char>& host);
+size_t so_work_bytes(int real_bytes, int n, int AH, int NH, int NMAX);

@@ -3,6 +3,7 @@
 // femean.F90:84-121, STHQ sthq.F90:75-120 and DOMINANT_PERIOD dominant_period.F90:76-112) -- and the OUTWNORM statistics (average / minimum / maximum / non-missing count, outwnorm.F90), so
 // that a device-resident run can be checked without copying the spectra back.
 #include "outbs_point.h"
+#include "launch.h"
 
 // One wavefront per point.  The spectrum goes through an LDS tile [M][NANG|1]; the sums over it are outbs_point (csrc/outbs_point.h).
 template <typename T>
@@ -62,8 +63,8 @@ template <typename T>
 int launch_outbs(const void* tab, int kijs, int kijl, const void* fl1, double zmiss, void* out, int NANG, int NFRE, hipStream_t s) {
   const int n = kijl - kijs;
   if (n <= 0) return 0;
+  if (!outbs_size_ok(NANG, NFRE, sizeof(T))) return 1;
   const size_t shmem = (size_t)4 * NFRE * (NANG | 1) * sizeof(T);
-  if (shmem > 64 * 1024) return 1;
   hipLaunchKernelGGL(k_outbs<T>, dim3((n + 3) / 4), dim3(256), shmem, s, (const DevTab<T>*)tab, kijs, kijl, (const T*)fl1, (T)zmiss, (T*)out);
   return 0;
 }

@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "outbs_fl2nd.h"
+#include "launch.h"
 
 #define SO_MAXNH 24  // NFREH at NFRE = MAXF = 48
 #define SO_MAXNX 32  // NMAX (28 at NFRE = 48)
@@ -315,7 +316,7 @@ int launch_outbs_second_order(const void* tab, const void* itab, const void* sot
                               double zmiss, void* out, void* fl2nd, int NANG, int NFRE, hipStream_t s) {
   const int n = kijl - kijs;
   if (n <= 0) return 0;
-  if ((size_t)4 * NFRE * (NANG | 1) * sizeof(T) > 64 * 1024 || NANG > 64 || NFRE > 63) return 1;
+  if (!outbs_size_ok(NANG, NFRE, sizeof(T))) return 1;
   const int AH = NANG / 2, NH = NFRE / 2;
   if (AH != 24 && AH != 18 && AH != 12 && AH != 6) return 1;
   const AbsLds L(NANG, NFRE, sizeof(T), mode & 1);

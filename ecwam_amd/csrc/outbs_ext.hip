@@ -12,6 +12,7 @@
 #include <algorithm>
 
 #include "dev.h"
+#include "launch.h"
 
 namespace {
 

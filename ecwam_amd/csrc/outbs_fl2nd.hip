@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "outbs_fl2nd.h"
+#include "launch.h"
 
 template <typename T>
 static T host_powi(T x, int n) {  // X**N as compilers expand it (binary powering), n >= 1
@@ -94,7 +95,7 @@ int launch_outbs_absolute(const void* tab, const void* itab, int kijs, int kijl,
                           const void* vcur, const void* ff, double zmiss, void* out, void* fl2nd, int NANG, int NFRE, hipStream_t s) {
   const int n = kijl - kijs;
   if (n <= 0) return 0;
-  if ((size_t)4 * NFRE * (NANG | 1) * sizeof(T) > 64 * 1024 || NANG > 64 || NFRE > 63) return 1;
+  if (!outbs_size_ok(NANG, NFRE, sizeof(T))) return 1;
   const AbsLds L(NANG, NFRE, sizeof(T), mode & 1);
   if (L.bytes > 64 * 1024) return 1;
   const int wpb = (int)std::min<size_t>(4, (size_t)64 * 1024 / L.bytes);

@@ -25,6 +25,7 @@
 #include <algorithm>
 
 #include "dev.h"
+#include "launch.h"
 
 namespace {
 
@@ -574,7 +575,7 @@ template <typename T>
 int launch_outbs_partition(const void* tab, int kijs, int kijl, const void* fl1, const void* xllws, const int* mij, const void* wvprpt,
                            const void* ff, double zmiss, void* out, int NANG, int NFRE, hipStream_t s) {
   const int n = kijl - kijs;
-  if ((size_t)4 * NFRE * (NANG | 1) * sizeof(T) > 64 * 1024 || NANG > 64 || NFRE > 63) return 1;
+  if (!outbs_size_ok(NANG, NFRE, sizeof(T))) return 1;
   if (n <= 0) return 0;
   const PartLds L(NANG, NFRE, sizeof(T));
   if (L.bytes > 64 * 1024) return 1;

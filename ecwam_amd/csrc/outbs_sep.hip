@@ -6,6 +6,7 @@
 #include <algorithm>
 
 #include "dev.h"
+#include "launch.h"
 
 __device__ __forceinline__ float m_fmod(float a, float b) { return fmodf(a, b); }
 __device__ __forceinline__ double m_fmod(double a, double b) { return fmod(a, b); }
@@ -267,7 +268,7 @@ int launch_outbs_sepwisw(const void* tab, int kijs, int kijl, const void* fl1, c
                          double zmiss, void* out, int NANG, int NFRE, hipStream_t s) {
   const int n = kijl - kijs;
   if (n <= 0) return 0;
-  if ((size_t)4 * NFRE * (NANG | 1) * sizeof(T) > 64 * 1024 || NANG > 64 || NFRE > 63) return 1;
+  if (!outbs_size_ok(NANG, NFRE, sizeof(T))) return 1;
   const SepLds L(NANG, NFRE, sizeof(T));
   const int wpb = (int)std::min<size_t>(4, (size_t)64 * 1024 / L.bytes);
   hipLaunchKernelGGL(k_outbs_sepwisw<T>, dim3((n + wpb - 1) / wpb), dim3(64 * wpb), wpb * L.bytes, s, (const DevTab<T>*)tab, kijs, kijl, wpb,

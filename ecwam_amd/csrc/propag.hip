@@ -9,6 +9,7 @@
 #include "dev.h"
 
 #include "ctu.h"
+#include "launch.h"
 
 template <typename T>
 __global__ void __launch_bounds__(256) k_propags2(const DevTab<T>* __restrict__ tab, const T* __restrict__ f1, T* __restrict__ f3,
@@ -1223,23 +1224,19 @@ void launch_propags2(const void* tab, const void* f1, void* f3, const int* klon,
                      klat, kcor, (const T*)w, kijs, kijl, m0, m1, copy_rest);
 }
 template <typename T>
-void launch_ctuw(const void* tab, int n, int nland, int ngy, double delpro, int m0, int m1, const int* kxlt, const void* zdello,
-                 double xdella, const void* cosph, const void* sinph, const int* klon, const int* klat, const int* kcor,
-                 void* wlat, void* wcor, const void* cg, const void* cosphm1, void* w, int* cflfail, int NANG, const void* obs,
+void launch_ctuw(const void* tab, int n, int nland, double delpro, int m0, int m1, const AdvGeom& g, void* w, int* cflfail, int NANG, const void* obs,
                  hipStream_t s) {
   if (n <= 0) return;
-  hipLaunchKernelGGL(k_ctuwini<T>, dim3((n + 255) / 256), dim3(256), 0, s, n, nland, klat, kcor, (T*)wlat, (T*)wcor);
+  hipLaunchKernelGGL(k_ctuwini<T>, dim3((n + 255) / 256), dim3(256), 0, s, n, nland, g.klat, g.kcor, (T*)g.wlat, (T*)g.wcor);      // (fills WLAT, WCOR)
   long long total = (long long)n * NANG * (m1 - m0);
-  hipLaunchKernelGGL(k_ctuw<T>, dim3(grid_for(total)), dim3(256), 0, s, (const DevTab<T>*)tab, n, ngy, (T)delpro, m0, m1, kxlt,
-                     (const T*)zdello, (T)xdella, (const T*)cosph, (const T*)sinph, klon, klat, (const T*)wlat, (const T*)wcor,
-                     (const T*)cg, (const T*)cosphm1, (T*)w, cflfail, (const T*)obs);
+  hipLaunchKernelGGL(k_ctuw<T>, dim3(grid_for(total)), dim3(256), 0, s, (const DevTab<T>*)tab, n, g.ngy, (T)delpro, m0, m1, g.kxlt,
+                     (const T*)g.zdello, (T)g.xdella, (const T*)g.cosph, (const T*)g.sinph, g.klon, g.klat, (const T*)g.wlat, (const T*)g.wcor,
+                     (const T*)g.cgroup_ext, (const T*)g.cosphm1_ext, (T*)w, cflfail, (const T*)obs);
 }
 template <typename T>
-void launch_propags2_otf(const void* tab, const void* f1, void* f3, int n_geom, int ngy, double delpro, const int* kxlt,
-                         const void* zdello, double xdella, const void* cosph, const void* sinph, const int* klon, const int* klat,
-                         const int* kcor, const void* wlat, const void* wcor, const void* cg, const void* cosphm1, const int* order,
-                         int kijs, int kijl, int m0, int m1, int copy_rest, int dims, const void* obs, int mlf, double delpro_lf, int in_k,
-                         void* gout, int gout_k, const void* gin, int gin_k, int out_k, hipStream_t s) {
+void launch_propags2_otf(const void* tab, const void* f1, void* f3, int n_geom, double delpro, const AdvGeom& g, const int* order, int kijs, int kijl, int m0,
+                         int m1, int copy_rest, int dims, const void* obs, int mlf, double delpro_lf, int in_k, void* gout, int gout_k, const void* gin,
+                         int gin_k, int out_k, hipStream_t s) {
   const int NANG = dims >> 16, NFRE = (dims >> 8) & 0xFF;
   if (in_k <= 0) in_k = NFRE;
   const int n = kijl - kijs;
@@ -1255,9 +1252,9 @@ void launch_propags2_otf(const void* tab, const void* f1, void* f3, int n_geom, 
   constexpr int W = VecOf<T>::W;
   const bool aligned = ((uintptr_t)f1 % 16 == 0) && ((uintptr_t)f3 % 16 == 0);
 #define OTF_ARGS                                                                                                              \
-  (const DevTab<T>*)tab, (const T*)f1, (T*)f3, n_geom, ngy, (T)delpro, kxlt, (const T*)zdello, (T)xdella, (const T*)cosph,     \
-      (const T*)sinph, klon, klat, kcor, (const T*)wlat, (const T*)wcor, (const T*)cg, (const T*)cosphm1, order, kijs, kijl, m0, \
-      m1, copy_rest, ntiles, (const T*)obs, mlf, (T)delpro_lf, in_k, (T*)gout, gout_k, (const T*)gin, gin_k, out_k
+  (const DevTab<T>*)tab, (const T*)f1, (T*)f3, n_geom, g.ngy, (T)delpro, g.kxlt, (const T*)g.zdello, (T)g.xdella, (const T*)g.cosph,               \
+      (const T*)g.sinph, g.klon, g.klat, g.kcor, (const T*)g.wlat, (const T*)g.wcor, (const T*)g.cgroup_ext, (const T*)g.cosphm1_ext, order, kijs, \
+      kijl, m0, m1, copy_rest, ntiles, (const T*)obs, mlf, (T)delpro_lf, in_k, (T*)gout, gout_k, (const T*)gin, gin_k, out_k
   int vw = W;
 #ifdef ECWAM_HIP_DIAGNOSTICS
   { const char* e_ = getenv("ECWAM_HIP_OTF_VW"); if (e_) vw = atoi(e_); }
@@ -1282,12 +1279,11 @@ void launch_ctuwini_only(int n, int nland, const int* klat, const int* kcor, voi
   hipLaunchKernelGGL(k_ctuwini<T>, dim3((n + 255) / 256), dim3(256), 0, s, n, nland, klat, kcor, (T*)wlat, (T*)wcor);
 }
 template <typename T>
-void launch_propdot(const void* tab, int n, int nland, int irefra, const int* kxlt, const void* zdello, double xdella, const void* cosph,
-                    const int* klon, const int* klat, const void* wlat, const void* cosphm1, const void* depth, const void* ue,
-                    const void* ve, void* refr, hipStream_t s) {
+void launch_propdot(const void* tab, int n, int nland, int irefra, const AdvGeom& g, const void* depth, const void* ue, const void* ve, void* refr,
+                    hipStream_t s) {
   if (n <= 0) return;
-  hipLaunchKernelGGL(k_propdot<T>, dim3((n + 127) / 128), dim3(128), 0, s, (const DevTab<T>*)tab, n, nland, irefra, kxlt,
-                     (const T*)zdello, (T)xdella, (const T*)cosph, klon, klat, (const T*)wlat, (const T*)cosphm1, (const T*)depth,
+  hipLaunchKernelGGL(k_propdot<T>, dim3((n + 127) / 128), dim3(128), 0, s, (const DevTab<T>*)tab, n, nland, irefra, g.kxlt,
+                     (const T*)g.zdello, (T)g.xdella, (const T*)g.cosph, g.klon, g.klat, (const T*)g.wlat, (const T*)g.cosphm1_ext, (const T*)depth,
                      (const T*)ue, (const T*)ve, (T*)refr);
 }
 template <typename T>
@@ -1297,11 +1293,9 @@ void launch_curmask(int n, int NANG, int slot, const int* cflfail, void* refr, h
 }
 // f1 == nullptr: CFL / range checks only (cflfail); else the stencil
 template <typename T>
-void launch_propags2_gen(const void* tab, int irefra, const void* f1, void* f3, int ngy, double delpro, const int* kxlt,
-                         const void* zdello, double xdella, const void* cosph, const void* sinph, const int* klon, const int* klat,
-                         const int* kcor, const void* wlat, const void* wcor, const void* cg, const void* om, const void* wn,
-                         const void* cosphm1, const void* refr, int* cflfail, int slot, int kijs, int kijl, int m0, int m1,
-                         int copy_rest, int dims, const void* obs, hipStream_t s) {
+void launch_propags2_gen(const void* tab, int irefra, const void* f1, void* f3, double delpro, const AdvGeom& g, const void* om, const void* wn,
+                         const void* refr, int* cflfail, int slot, int kijs, int kijl, int m0, int m1, int copy_rest, int dims, const void* obs,
+                         hipStream_t s) {
   const int NANG = dims >> 16, NFRE = (dims >> 8) & 0xFF, NR = dims & 0xFF;
   const int n = kijl - kijs;
   if (n <= 0) return;
@@ -1312,9 +1306,9 @@ void launch_propags2_gen(const void* tab, int irefra, const void* f1, void* f3, 
   constexpr int W = VecOf<T>::W;
   const bool aligned = ((uintptr_t)f1 % 16 == 0) && ((uintptr_t)f3 % 16 == 0);
 #define GEN_ARGS                                                                                                               \
-  (const DevTab<T>*)tab, irefra, (const T*)f1, (T*)f3, ngy, (T)delpro, kxlt, (const T*)zdello, (T)xdella, (const T*)cosph,       \
-      (const T*)sinph, klon, klat, kcor, (const T*)wlat, (const T*)wcor, (const T*)cg, (const T*)om, (const T*)wn,             \
-      (const T*)cosphm1, (const T*)refr, cflfail, slot, kijs, kijl, m0, m1, copy_rest, ntiles, (const T*)obs
+  (const DevTab<T>*)tab, irefra, (const T*)f1, (T*)f3, g.ngy, (T)delpro, g.kxlt, (const T*)g.zdello, (T)g.xdella, (const T*)g.cosph,           \
+      (const T*)g.sinph, g.klon, g.klat, g.kcor, (const T*)g.wlat, (const T*)g.wcor, (const T*)g.cgroup_ext, (const T*)om, (const T*)wn,       \
+      (const T*)g.cosphm1_ext, (const T*)refr, cflfail, slot, kijs, kijl, m0, m1, copy_rest, ntiles, (const T*)obs
   // 8 bytes per lane is the fastest width here (measured at O320 sp: 7.9 ms, against 9.2 ms at 16 bytes and 9.0 ms scalar):
   // the VW sets of 21 weights a thread keeps live cost more occupancy than the wider accesses save
   int vw = 2;
@@ -1379,12 +1373,10 @@ __global__ void k_ctu_prep(const DevTab<T>* __restrict__ tab, int kijs, int kijl
   }
 }
 template <typename T>
-void launch_ctu_prep(const void* tab, int kijs, int kijl, int ngy, double delpro, double delpro_lf, const int* kxlt, const void* zdello, double xdella,
-                     const void* cosph, const void* sinph, const void* wlat, const void* wcor, const void* cosphm1, void* pt, void* dirT, int* dirI,
-                     hipStream_t s) {
+void launch_ctu_prep(const void* tab, int kijs, int kijl, double delpro, double delpro_lf, const AdvGeom& g, void* pt, void* dirT, int* dirI, hipStream_t s) {
   const int n = kijl - kijs;
-  hipLaunchKernelGGL(k_ctu_prep<T>, dim3(n > 0 ? grid_for(n) : 1), dim3(256), 0, s, (const DevTab<T>*)tab, kijs, kijl, ngy, (T)delpro, (T)delpro_lf, kxlt,
-                     (const T*)zdello, (T)xdella, (const T*)cosph, (const T*)sinph, (const T*)wlat, (const T*)wcor, (const T*)cosphm1, (T*)pt,
+  hipLaunchKernelGGL(k_ctu_prep<T>, dim3(n > 0 ? grid_for(n) : 1), dim3(256), 0, s, (const DevTab<T>*)tab, kijs, kijl, g.ngy, (T)delpro, (T)delpro_lf, g.kxlt,
+                     (const T*)g.zdello, (T)g.xdella, (const T*)g.cosph, (const T*)g.sinph, (const T*)g.wlat, (const T*)g.wcor, (const T*)g.cosphm1_ext, (T*)pt,
                      (T*)dirT, dirI);
 }
 // NO SOURCE TERM CONTRIBUTION (wamintgr.F90:152-160): FL1 = MAX(FL1, EPSMIN), MIJ = NFRE, XLLWS = 0 on rows [kijs, kijl)
@@ -1449,24 +1441,17 @@ void launch_proenv_unpack(int nrows, int NFRE, const void* buf, const void* land
   template void launch_proenv_unpack<T>(int, int, const void*, const void*, void*, void*, void*, void*, void*, void*, hipStream_t); \
   template void launch_propags2<T>(const void*, const void*, void*, const int*, const int*, const int*, const void*, int, int,   \
                                    int, int, int, int, hipStream_t);                                                              \
-  template void launch_ctuw<T>(const void*, int, int, int, double, int, int, const int*, const void*, double, const void*,       \
-                               const void*, const int*, const int*, const int*, void*, void*, const void*, const void*, void*,   \
-                               int*, int, const void*, hipStream_t);                                                              \
+  template void launch_ctuw<T>(const void*, int, int, double, int, int, const AdvGeom&, void*, int*, int, const void*, hipStream_t); \
   template void launch_newwind<T>(const void*, int, void*, const void*, int, hipStream_t);                                        \
-  template void launch_ctu_prep<T>(const void*, int, int, int, double, double, const int*, const void*, double, const void*, const void*, const void*, const void*, const void*, void*, void*, int*, hipStream_t);\
+  template void launch_ctu_prep<T>(const void*, int, int, double, double, const AdvGeom&, void*, void*, int*, hipStream_t);       \
   template void launch_nosource<T>(const void*, int, int, int, void*, void*, int*, hipStream_t);                                  \
-  template void launch_propdot<T>(const void*, int, int, int, const int*, const void*, double, const void*, const int*,         \
-                                  const int*, const void*, const void*, const void*, const void*, const void*, void*, hipStream_t); \
+  template void launch_propdot<T>(const void*, int, int, int, const AdvGeom&, const void*, const void*, const void*, void*, hipStream_t); \
   template void launch_ctuwini_only<T>(int, int, const int*, const int*, void*, void*, hipStream_t);                               \
   template void launch_curmask<T>(int, int, int, const int*, void*, hipStream_t);                                                      \
-  template void launch_propags2_gen<T>(const void*, int, const void*, void*, int, double, const int*, const void*, double,        \
-                                       const void*, const void*, const int*, const int*, const int*, const void*, const void*,   \
-                                       const void*, const void*, const void*, const void*, const void*, int*, int, int, int, int, \
-                                       int, int, int, const void*, hipStream_t);                                                                    \
-  template void launch_propags2_otf<T>(const void*, const void*, void*, int, int, double, const int*, const void*, double,        \
-                                       const void*, const void*, const int*, const int*, const int*, const void*, const void*,   \
-                                       const void*, const void*, const int*, int, int, int, int, int, int, const void*, int, double,   \
-                                       int, void*, int, const void*, int, int, hipStream_t);                                                                              \
+  template void launch_propags2_gen<T>(const void*, int, const void*, void*, double, const AdvGeom&, const void*, const void*, const void*, int*, int, int, \
+                                       int, int, int, int, int, const void*, hipStream_t);                                        \
+  template void launch_propags2_otf<T>(const void*, const void*, void*, int, double, const AdvGeom&, const int*, int, int, int, int, int, int, const void*, \
+                                       int, double, int, void*, int, const void*, int, int, hipStream_t);                         \
   template void launch_c2p<T>(const void*, void*, int, int, int, int, int, hipStream_t);                                          \
   template void launch_p2c<T>(const void*, void*, int, int, int, int, int, hipStream_t);                                          \
   template void launch_copy_freq_range<T>(const void*, void*, int, int, int, int, int, int, hipStream_t);                             \
