@@ -25,6 +25,10 @@ OUTBS_PART_FIELDS = OUTBS_SEP_FIELDS + ("swh1", "mwd1", "mwp1", "swh2", "mwd2", 
 OUTBS_EXT_FIELDS = ("c4", "bfi", "qp", "hmax", "tmax", "c3", "eta_m", "r", "xnslc", "cmax_f", "hmax_n", "cmax_st", "hmax_st")
 # columns of ecwam_hip_outbs_absolute (include/ecwam_hip.h): OUTBLOCK parameters 1, 2, 3, EM, 6, 20, 21, 22 of the output spectrum FL2ND
 OUTBS_ABS_FIELDS = ("swh", "mwd", "mwp", "em", "pp1d", "mp1", "mp2", "wdw")
+# the first eight columns of ecwam_hip_outbs_integrals (the bands follow) and its column groups (flags)
+OUTBS_INT_FIELDS = ("cd", "tauw_n", "mss", "strn", "wefmag", "wefdir", "ctcor", "mss_m")
+OUTBS_INT_GROUPS = dict(slopes=1, strain=2, flux=4, ctcor=8, bands=16, point=32)
+OUTBS_INT_ALL = 63
 
 
 class EcwamHipError(RuntimeError):
@@ -396,6 +400,60 @@ class HipContext:
                                                         self._real(out, (out.shape[0], len(OUTBS_ABS_FIELDS)), "OUT"),
                                                         opt(fl2nd, (0 if fl2nd is None else fl2nd.shape[0], self.NANG, self.NFRE), "FL2ND"),
                                                         _stream_ptr()))
+
+    # -- OUTBLOCK's remaining spectral integrals (ecwam_hip_outbs_integrals) and OUTSETWMASK
+    @property
+    def integral_bands(self):
+        """The (TB, TT) bands of the last set_outbs_integrals(), None before it."""
+        return getattr(self, "_int_bands", None)
+
+    def default_bands(self):
+        """The reference's seven bands: SE10MEAN = (10, 1/FR(1)), then 10-12, 12-14, 14-17, 17-21, 21-25 and 25-30 s (outblock.F90:460, 515-519)."""
+        return [(10.0, float(np.dtype(self.t.dtype).type(1.0) / self.t.FR[0]))] + [(10.0, 12.0), (12.0, 14.0), (14.0, 17.0), (17.0, 21.0), (21.0, 25.0), (25.0, 30.0)]
+
+    def set_outbs_integrals(self, xkmss_cutoff: float = 0.0, bands=None) -> None:
+        """The cut-off of the mean square slope (<= 0: XK_GC(NWAV_GC)) and the period bands [(TB, TT), ...] of outbs_integrals();
+        bands = None: default_bands().  Uploads DELKCC_GC of the context's tables."""
+        bands = self.default_bands() if bands is None else [(float(a), float(b)) for a, b in bands]
+        tb = np.ascontiguousarray([b[0] for b in bands], dtype=np.float64)
+        tt = np.ascontiguousarray([b[1] for b in bands], dtype=np.float64)
+        d = np.ascontiguousarray(self.t.DELKCC_GC, dtype=self.t.dtype)
+        self._int_bands = None      # a refused call leaves the previous table in the library, but this layer forgets it
+        self._chk(self.lib.ecwam_hip_set_outbs_integrals(self._h, float(xkmss_cutoff), len(bands), tb.ctypes.data if len(bands) else None,
+                                                         tt.ctypes.data if len(bands) else None, d.ctypes.data))
+        self._int_bands = bands
+
+    def outbs_integrals(self, kijs, kijl, fl1, wvprpt, ff, out, fl2nd=None, groups=OUTBS_INT_ALL, zmiss: float = -999.0):
+        """Drag, normalised wave stress, mean square slopes, ice strain, energy flux, crest-trough correlation and band heights
+        (ecwam_hip_outbs_integrals) of rows [kijs, kijl) into out[:, 8 + nband], columns OUTBS_INT_FIELDS then the bands.  fl2nd: the output
+        spectrum stored by outbs_absolute() / outbs_second_order() for the bands, None: FL1.  groups: a sum of OUTBS_INT_GROUPS values."""
+        rows = [out.shape[0]] + [a.shape[0] for a in (fl1, wvprpt, ff, fl2nd) if a is not None]
+        if not (0 <= kijs <= kijl <= min(rows)):
+            raise ValueError("OUTBS_INTEGRALS: KIJS/KIJL outside the operands")
+        opt = lambda a, shape, name: None if a is None else self._real(a, shape, name)
+        nb = len(self._int_bands) if self.integral_bands is not None else out.shape[1] - len(OUTBS_INT_FIELDS)
+        a = [opt(fl1, (0 if fl1 is None else fl1.shape[0], self.NANG, self.NFRE), "FL1"),
+             opt(fl2nd, (0 if fl2nd is None else fl2nd.shape[0], self.NANG, self.NFRE), "FL2ND"),
+             opt(wvprpt, (0 if wvprpt is None else wvprpt.shape[0], NWPR, self.NFRE), "WVPRPT"), opt(ff, (0 if ff is None else ff.shape[0], NFF), "FF")]
+        self._chk(self.lib.ecwam_hip_outbs_integrals(self._h, kijs, kijl, *a, int(groups), float(zmiss),
+                                                     self._real(out, (out.shape[0], len(OUTBS_INT_FIELDS) + nb), "OUT"), _stream_ptr()))
+
+    def outsetwmask(self, kijs, kijl, out, colflags, ff=None, iodp=None, cithrsh: float | None = None, zmiss: float = -999.0):
+        """OUTSETWMASK (ecwam_hip_outsetwmask) on rows [kijs, kijl) of an output buffer, in place.  colflags: per column, 1 = sea-ice mask
+        (zmiss where CICOVER = ff[:, 2] > cithrsh; only with LICERUN), 2 = sea mask out*IODP + (1-IODP)*zmiss, 3 = both.  cithrsh: default
+        CITHRSH of the tables."""
+        if not (out.is_cuda and out.dtype == self.dtype and out.is_contiguous() and out.dim() == 2):
+            raise ValueError("OUTSETWMASK: expected a contiguous 2-D cuda tensor in the working precision")
+        cf = np.ascontiguousarray(colflags, dtype=np.int32)
+        if cf.shape != (out.shape[1],):
+            raise ValueError("OUTSETWMASK: one flag per column")
+        rows = [out.shape[0]] + [a.shape[0] for a in (ff, iodp) if a is not None]
+        if not (0 <= kijs <= kijl <= min(rows)):
+            raise ValueError("OUTSETWMASK: KIJS/KIJL outside the operands")
+        pff = None if ff is None else self._real(ff, (ff.shape[0], NFF), "FF")
+        pio = None if iodp is None else self._int(iodp, (iodp.shape[0],), "IODP")
+        self._chk(self.lib.ecwam_hip_outsetwmask(self._h, kijs, kijl, out.data_ptr(), out.shape[1], cf.ctypes.data, pff, pio,
+                                                 float(self.t.CITHRSH if cithrsh is None else cithrsh), float(zmiss), _stream_ptr()))
 
     def outwnorm(self, field, column: int, n: int, zmiss: float = -999.0):
         """(average, minimum, maximum, count) of field[:n, column] over the values != zmiss."""

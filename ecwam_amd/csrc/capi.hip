@@ -79,6 +79,9 @@ struct ecwam_hip_ctx {
   size_t so_work_bytes = 0;
   int so_nmax = 0;
   std::vector<unsigned char> fr_host;  // FR(1:NFRE) in the working precision
+  // ecwam_hip_set_outbs_integrals (csrc/outbs_int.hip): IntTab<T> in device memory; the number of bands, -1 before the setter is called
+  void* int_tab = nullptr;
+  int int_nband = -1;
   const void* obs = nullptr;  // LSUBGRID: device OBS[n_obs][8][NFRE] (ecwam_hip_set_obstructions), read by CTUW / PROPAGS2
   int n_obs = 0;
 };
@@ -504,6 +507,7 @@ int ecwam_hip_destroy(ecwam_hip_ctx* c) {
   if (c->so_tab) (void)hipFree(c->so_tab);
   if (c->so_coef) (void)hipFree(c->so_coef);
   if (c->so_work) (void)hipFree(c->so_work);
+  if (c->int_tab) (void)hipFree(c->int_tab);
   if (c->fin) (void)hipFree(c->fin);
   if (c->wi) (void)hipFree(c->wi);
   if (c->adv_pt) (void)hipFree(c->adv_pt);
@@ -975,6 +979,59 @@ int ecwam_hip_outbs_second_order(ecwam_hip_ctx* c, int kijs, int kijl, const voi
                                                   ff, sig, zmiss, out, fl2nd, c->NANG, c->NFRE, s);
   });
   return outbs_tail(rc, "ecwam_hip_outbs_second_order: unsupported spectral size (NANG must be 48, 36, 24 or 12)");
+}
+
+int ecwam_hip_set_outbs_integrals(ecwam_hip_ctx* c, double xkmss_cutoff, int nband, const double* tb, const double* tt, const void* delkcc_gc) {
+  if (!c) return fail("null context");
+  if (nband < 0 || nband > 8) return fail("ecwam_hip_set_outbs_integrals: nband must be 0 .. 8");
+  if (!delkcc_gc || (nband && (!tb || !tt))) return fail("ecwam_hip_set_outbs_integrals: null pointer");
+  HIPCHK(hipSetDevice(c->device));
+  HIPCHK(hipDeviceSynchronize());   // no call in flight reads the table that is replaced
+  std::vector<unsigned char> dt(outbs_devtab_bytes(c->real_bytes)), h;
+  HIPCHK(hipMemcpy(dt.data(), c->dtab, dt.size(), hipMemcpyDeviceToHost));
+  const char* why = outbs_int_tab_build(dt.data(), c->real_bytes, xkmss_cutoff, nband, tb, tt, delkcc_gc, h);
+  if (why) return fail((std::string("ecwam_hip_set_outbs_integrals: ") + why).c_str());
+  if (!c->int_tab) HIPCHK(hipMalloc(&c->int_tab, h.size()));
+  HIPCHK(hipMemcpy(c->int_tab, h.data(), h.size(), hipMemcpyHostToDevice));
+  c->int_nband = nband;
+  return 0;
+}
+
+int ecwam_hip_outbs_integrals(ecwam_hip_ctx* c, int kijs, int kijl, const void* fl1, const void* fl2nd, const void* wvprpt, const void* ff, int flags,
+                              double zmiss, void* out, void* stream) {
+  if (outbs_head(c, kijs, kijl, "ecwam_hip_outbs_integrals: bad range")) return 1;
+  if (flags & ~63) return fail("ecwam_hip_outbs_integrals: unknown flags");
+  if (c->int_nband < 0) return fail("ecwam_hip_outbs_integrals: the cut-off and the bands are not set (ecwam_hip_set_outbs_integrals)");
+  if ((flags & 16) && c->int_nband == 0) return fail("ecwam_hip_outbs_integrals: the band group is selected but no band is set (nband = 0)");
+  if (c->NANG != 48 && c->NANG != 36 && c->NANG != 24 && c->NANG != 12) return fail("ecwam_hip_outbs_integrals: no build for this NANG (48, 36, 24 and 12 are built)");
+  if (kijl > kijs && !out) return fail("ecwam_hip_outbs_integrals: null pointer");
+  if (kijl > kijs && (flags & (1 | 2 | 4 | 8)) && (!fl1 || !wvprpt || !ff)) return fail("ecwam_hip_outbs_integrals: the readers of FL1 need fl1, wvprpt and ff");
+  if (kijl > kijs && (flags & 32) && !ff) return fail("ecwam_hip_outbs_integrals: the point-wise group needs ff");
+  if (kijl > kijs && (flags & 16) && !fl1 && !fl2nd) return fail("ecwam_hip_outbs_integrals: the bands need fl2nd or fl1");
+  if (!fl2nd) fl2nd = fl1;
+  if (!fl1) fl1 = fl2nd;   // bands only: the one row that is read
+  const int rc = in_precision(c, [&](auto t) { return launch_outbs_integrals<decltype(t)>(c->dtab, c->int_tab, kijs, kijl, fl1, fl2nd, wvprpt, ff, flags, zmiss, out, c->NANG, c->NFRE, (hipStream_t)stream); });
+  return outbs_tail(rc, "ecwam_hip_outbs_integrals: unsupported spectral size");
+}
+
+int ecwam_hip_outsetwmask(ecwam_hip_ctx* c, int kijs, int kijl, void* out, int ncol, const int* colflags, const void* ff, const int* iodp, double cithrsh,
+                          double zmiss, void* stream) {
+  if (outbs_head(c, kijs, kijl, "ecwam_hip_outsetwmask: bad range")) return 1;
+  if (ncol < 1 || ncol > 64) return fail("ecwam_hip_outsetwmask: ncol must be 1 .. 64");
+  if (!colflags || (kijl > kijs && !out)) return fail("ecwam_hip_outsetwmask: null pointer");
+  OutMaskCols cols;
+  int any = 0;
+  for (int i = 0; i < 64; i++) cols.f[i] = 0;
+  for (int i = 0; i < ncol; i++) {
+    if (colflags[i] & ~3) return fail("ecwam_hip_outsetwmask: unknown column flags");
+    cols.f[i] = (unsigned char)colflags[i];
+    any |= colflags[i];
+  }
+  const int ice = c->p.licerun != 0;   // LICERUN .AND. LLSOURCE: the library integrates the source terms
+  if (kijl > kijs && (any & 2) && !iodp) return fail("ecwam_hip_outsetwmask: a column has the sea mask but iodp is NULL");
+  if (kijl > kijs && ice && (any & 1) && !ff) return fail("ecwam_hip_outsetwmask: the sea-ice mask needs ff (CICOVER)");
+  in_precision(c, [&](auto t) { launch_outsetwmask<decltype(t)>(kijs, kijl, out, ncol, cols, ff, iodp, ice, cithrsh, zmiss, (hipStream_t)stream); });
+  return launched();
 }
 
 int ecwam_hip_outwnorm(ecwam_hip_ctx* c, const void* field, int stride, int n, double zmiss, double* result, void* stream) {

@@ -76,6 +76,15 @@ template <typename T> int launch_outbs_absolute(const void* tab, const void* ita
 template <typename T> int launch_outbs_second_order(const void* tab, const void* itab, const void* sotab, const void* coef, void* work, int nmax, int kijs, int kijl, int mode,
         const void* fl1, const void* wvprpt, const void* depth, const void* ucur, const void* vcur, const void* ff, double sig, double zmiss, void* out, void* fl2nd, int NANG, int NFRE,
         hipStream_t s);
+template <typename T> int launch_outbs_integrals(const void* tab, const void* inttab, int kijs, int kijl, const void* fl1, const void* fl2nd, const void* wvprpt, const void* ff,
+        int flags, double zmiss, void* out, int NANG, int NFRE, hipStream_t s);   // 2 = no build for NANG
+struct OutMaskCols { unsigned char f[64]; };   // OUTSETWMASK: per column, bit 0 the sea-ice mask, bit 1 the sea mask
+template <typename T> void launch_outsetwmask(int kijs, int kijl, void* out, int ncol, const OutMaskCols& cols, const void* ff, const int* iodp, int ice, double cithrsh,
+        double zmiss, hipStream_t s);
+// IntTab<T> (csrc/outbs_int.h) from a host copy of DevTab<T>; a refusal's reason, or NULL
+const char* outbs_int_tab_build(const void* devtab_host, int real_bytes, double xkmss_cutoff, int nband, const double* tbnd, const double* ttop, const void* delkcc_gc,
+        std::vector<unsigned char>& host);
+size_t outbs_devtab_bytes(int real_bytes);
 size_t intpol_tab_build(const ecwam_hip_params* p, const ecwam_hip_tables* t, int real_bytes, std::vector<unsigned char>& host);
 const char* so_tab_build(const ecwam_hip_params* p, const void* fr, int real_bytes, int ndepth, double deptha, double depthd, int nmax, const int* im_p, const int* im_m,
         std::vector<unsigned char>& host);

@@ -4,6 +4,20 @@
 #pragma once
 #include "dev.h"
 
+// FEMEAN's sums over frequency and its tail (femean.F90:105-120) from t2 = the sum over K of MAX(F(K,M),EPSMIN) that lane M holds: shared by
+// outbs_point below and by k_outbs_integrals (csrc/outbs_int.hip: FEMEAN of the wind half plane, halphap.F90:89).
+template <typename T>
+__device__ __forceinline__ void femean_of_rowsums(const DevTab<T>& tb, T t2, int lane, T& EM, T& FM) {
+  const int NFRE = tb.NFRE;
+  const bool actm = lane < NFRE;
+  usum2(actm ? t2 * tb.DFIM[lane] : T(0), actm ? tb.DFIMOFR[lane] * t2 : T(0), EM, FM);
+  const T tl = lane_get(t2, NFRE - 1);
+  EM = EM + tb.WETAIL * tb.FR[NFRE - 1] * tb.DELTH * tl;
+  FM = FM + tb.FRTAIL * tb.DELTH * tl;
+  FM = EM / FM;
+  FM = m_max(FM, tb.FR[0]);
+}
+
 // One wavefront per point; sF = the tile [M][NANG|1], complete and visible to the wave.  lane = M sums MAX(F,EPSMIN) over K in the
 // reference's order (FEMEAN), lane = K sums F*DFIM over M in the reference's order (STHQ).  Lane 0 writes o[0..4] = significant wave
 // height, mean direction [degrees], mean period or zmiss, EM, peak period or zmiss.
@@ -19,12 +33,7 @@ __device__ __forceinline__ void outbs_point(const DevTab<T>& tb, const T* sF, in
     for (int kk = 1; kk < NANG; kk++) t2 = t2 + m_max(p[kk], tb.EPSMIN);
   }
   T EM, FM;
-  usum2(actm ? t2 * tb.DFIM[lane] : T(0), actm ? tb.DFIMOFR[lane] * t2 : T(0), EM, FM);
-  const T tl = lane_get(t2, NFRE - 1);
-  EM = EM + tb.WETAIL * tb.FR[NFRE - 1] * tb.DELTH * tl;
-  FM = FM + tb.FRTAIL * tb.DELTH * tl;
-  FM = EM / FM;
-  FM = m_max(FM, tb.FR[0]);
+  femean_of_rowsums(tb, t2, lane, EM, FM);
   // STHQ
   T temp = T(0);
   if (actk)

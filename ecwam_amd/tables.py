@@ -509,6 +509,7 @@ class Tables:
         d[-1] = T(0.5) * (xk[-1] - xk[-2]) / self.C2OSQRTVG_GC[-1]
         dns[-1] = d[-1]
         self.DELKCC_GC_NS = dns
+        self.DELKCC_GC = d            # MEANSQS_GC sums it on its own (ecwam_hip_set_outbs_integrals)
         self.DELKCC_OMXKM3_GC = d * self.OMXKM3_GC
 
     def _ctu_selectors(self) -> None:

@@ -20,6 +20,7 @@ OUTBS_SEP_FIELDS = api.OUTBS_SEP_FIELDS     # the columns of Wamintgr.outbs_sepw
 OUTBS_EXT_FIELDS = api.OUTBS_EXT_FIELDS     # the columns of Wamintgr.outbs_extremes()
 OUTBS_PART_FIELDS = api.OUTBS_PART_FIELDS   # the columns of Wamintgr.outbs_partition()
 OUTBS_ABS_FIELDS = api.OUTBS_ABS_FIELDS     # the columns of Wamintgr.outbs_absolute()
+OUTBS_INT_FIELDS = api.OUTBS_INT_FIELDS     # the first eight columns of Wamintgr.outbs_integrals(); the bands follow
 
 
 class HaloExchange:
@@ -627,6 +628,16 @@ class Wamintgr:
         u, v = (self.u_ext, self.v_ext) if self.irefra >= 2 else (None, None)
         self.ctx.outbs_second_order(0, self.n, self.fl1, self.wvprpt, depth, u, v, self.ff, out, fl2nd=fl2nd, sig=sig)
         return (out, fl2nd) if store_spectrum else out
+
+    # ---- drag, normalised wave stress, mean square slopes, ice strain, energy flux, crest-trough correlation and the band heights on the
+    # device: [n][8 + nband], columns api.OUTBS_INT_FIELDS then the bands of ctx.integral_bands (set on first use: the reference's seven and
+    # XKMSS_CUTOFF = XK_GC(NWAV_GC)).  fl2nd: the spectrum outbs_absolute / outbs_second_order(store_spectrum=True) returned, for the bands
+    def outbs_integrals(self, fl2nd=None, groups: int = api.OUTBS_INT_ALL) -> torch.Tensor:
+        if self.ctx.integral_bands is None:
+            self.ctx.set_outbs_integrals()
+        out = torch.zeros((self.n, len(api.OUTBS_INT_FIELDS) + len(self.ctx.integral_bands)), dtype=self.dtype, device=self.dev)
+        self.ctx.outbs_integrals(0, self.n, self.fl1, self.wvprpt, self.ff, out, fl2nd=fl2nd, groups=groups)
+        return out
 
     def swh_norm(self):
         return self.ctx.outwnorm(self.outbs(), 0, self.n)

@@ -450,6 +450,66 @@ int ecwam_hip_outbs_second_order(ecwam_hip_ctx *ctx, int kijs, int kijl, const v
                                  const void *ucur, const void *vcur, const void *ff, double sig, double zmiss, void *out, void *fl2nd,
                                  void *stream);
 
+/*
+ * The constants of ecwam_hip_outbs_integrals, worked out once in the working precision and kept on the device.  Host arrays are copied
+ * before the call returns.
+ *   xkmss_cutoff   XKMSS_CUTOFF of YOWFRED, the wavenumber up to which parameter 9 integrates the slope; <= 0 selects XK_GC(NWAV_GC) as
+ *                  userin.F90:1214 does.  The second cut-off, (ZPI FR(NFRE))**2 / G of parameter 83 (outblock.F90:602), needs no argument.
+ *   nband, tb, tt  0 .. 8 period bands as SEBTMEAN's arguments: tb[i] the shorter and tt[i] the longer period [s] of band i (host doubles,
+ *                  rounded to the working precision).  The reference's seven: (10, 1/FR(1)) = SE10MEAN, then (10,12) (12,14) (14,17) (17,21)
+ *                  (21,25) (25,30) (outblock.F90:460, 515-519).  Per band the library precomputes MCUTB, MCUTT, FRLOC, the interpolation
+ *                  weights WL / WR at the two cut frequencies, the DF of the trapezoid, the factor of the linear front tail and ZW of the
+ *                  f**-5 extension, in sebtmean.F90:81-102,172-184's order of operations.
+ *   delkcc_gc      reals [NWAV_GC] of the working precision: DELKCC_GC of YOWFRED (initgc.F90), the one gravity-capillary table
+ *                  ecwam_hip_tables carries only as its product with OMXKM3_GC; MEANSQS_GC sums DELKCC_GC(I) XKM_GC(I).
+ * NE of MEANSQS_GC and NFRE_MSS of MEANSQS (meansqs_gc.F90:59, meansqs.F90:100) are evaluated in double precision from the working-precision
+ * tables: with the model's own cut-off the argument of INT lies within rounding of NFRE - 1, where the working-precision value would depend
+ * on the last bit of the logarithm routine at hand.
+ * Refused with a reason: nband outside 0 .. 8, tb > tt, a band wholly below FR(1) (SEBTMEAN would read FR(0)), a cut-off below FR(1).
+ * Synchronises the device; not thread safe against calls in flight on the context.
+ */
+int ecwam_hip_set_outbs_integrals(ecwam_hip_ctx *ctx, double xkmss_cutoff, int nband, const double *tb, const double *tt, const void *delkcc_gc);
+
+/*
+ * OUTBLOCK's remaining spectral integrals for rows [kijs,kijl) in ONE pass over the spectrum (outblock.F90:266-287, 451-462, 500-523, 597-604):
+ * OUTBETA (CD=), MEANSQS (HALPHAP, MEANSQS_GC with OMEGAGC, MEANSQS_LF, the tail) at both cut-offs, CIMSSTRN (AKI_ICE), WEFLUX, CTCOR of FL1,
+ * and SEBTMEAN / SE10MEAN of the output spectrum FL2ND.  Inputs: fl1; fl2nd -- NULL or equal to fl1: FL2ND = FL1 and the row is read once;
+ * else the spectrum stored by ecwam_hip_outbs_absolute or ecwam_hip_outbs_second_order (read once more, by the bands only); WAVNUM =
+ * wvprpt[ij][0][:], CGROUP = wvprpt[ij][1][:]; ff: WDWAVE [1], WSWAVE [3], UFRIC [7], TAUW [8], CHRNCK [12], CITHICK [13], DEPTH [15].
+ * out[npts][8 + nband] indexed by the absolute row ij (columns; OUTBLOCK parameter numbers with NTRAIN = 3 in brackets):
+ *    0 cd     MIN(CD of OUTBETA, 0.01) [7]                 1 tauw_n  TAUW / MAX(UFRIC**2, EPSUS) [8]
+ *    2 mss    mean square slope up to XKMSS_CUTOFF [9]     3 strn    mean square strain in the ice, CIMSSTRN [51]; with LWNEMOCOUSTRN the
+ *                                                                    reference outputs STRNMS of INTF instead: the host's choice
+ *    4 wefmag wave energy flux magnitude [62]              5 wefdir  its direction, MOD(DEG*WEFDIR+180,360) [63]
+ *    6 ctcor  crest-trough correlation or zmiss [82]       7 mss_m   mean square slope up to (ZPI FR(NFRE))**2 / G [83]
+ *    8 + i    4*SQRT(MAX(E,0)) of band i [52, 64-69 with the seven bands above]
+ * flags: the column groups to compute, so that a host pays only for what IPFGTBL asks -- 1 slopes (2, 7), 2 strain (3), 4 flux (4, 5),
+ * 8 CTCOR (6), 16 bands (8 ...), 32 point-wise (0, 1).  Columns of unselected groups are not written; a group's columns are the same bits
+ * whatever else is selected.  Other bits: error.  With only the bands selected fl1 or fl2nd alone suffices (wvprpt and ff may be NULL); with
+ * only the point-wise group ff alone.
+ * Every sum over K and over M runs in the reference's order of additions (FEMEAN of the wind half plane inside HALPHAP is the exception: it is
+ * the wavefront reduction the other output kernels use); no atomics: results do not depend on scheduling.
+ * Refused with a reason: bad range, ecwam_hip_set_outbs_integrals not called, the bands selected with nband = 0, NANG not 48 / 36 / 24 / 12,
+ * unknown flags.  The spectral sizes of ecwam_hip_outbs_sepwisw.  Not served: OUTSETWMASK (ecwam_hip_outsetwmask below).  OUTWNORM statistics
+ * of a column: ecwam_hip_outwnorm(out + column, stride = 8 + nband).
+ */
+int ecwam_hip_outbs_integrals(ecwam_hip_ctx *ctx, int kijs, int kijl, const void *fl1, const void *fl2nd, const void *wvprpt, const void *ff,
+                              int flags, double zmiss, void *out, void *stream);
+
+/*
+ * OUTSETWMASK (outsetwmask.F90:57-75; outblock.F90:610) on rows [kijs,kijl) of any of the library's output buffers out[npts][ncol], in place.
+ *   colflags  HOST int[ncol]: bit 0 -- the sea-ice mask applies to the column (IPRMINFO(IR,6) = 1), bit 1 -- the sea mask (IPRMINFO(IR,7) = 1);
+ *             copied before the call returns; ncol <= 64.
+ *   sea-ice mask: out = zmiss where CICOVER = ff[ij][2] > cithrsh (CITHRSH).  Applied only when the context has LICERUN; LLSOURCE, the
+ *             reference's other condition, is not a parameter of the library (it integrates the source terms): a host that runs the
+ *             LLSOURCE = F branch clears bit 0.
+ *   sea mask: out = out*IODP + (1-IODP)*zmiss, exactly as written there.  iodp: device int[>= kijl]; may be NULL when no column has bit 1.
+ * The sea-ice mask is applied first, as in the reference.  ff may be NULL when no column has bit 0 or the context has no LICERUN.
+ * OUTWNORM statistics of a masked column: ecwam_hip_outwnorm(out + column, stride = ncol) skips the zmiss values.
+ */
+int ecwam_hip_outsetwmask(ecwam_hip_ctx *ctx, int kijs, int kijl, void *out, int ncol, const int *colflags, const void *ff, const int *iodp,
+                          double cithrsh, double zmiss, void *stream);
+
 /* NEWWIND forcing hand-over (newwind.F90:126-161): FF <- FF_NEXT members + TAUW cap.  ecwam_hip_newwind takes ICODE_WND = ICODE
  * of the parameters; a coupled host (LWCOU) passes ICODE_CPL through ecwam_hip_newwind_icode (newwind.F90:120-124). */
 int ecwam_hip_newwind(ecwam_hip_ctx *ctx, int n, void *ff, const void *ff_next, void *stream);
