@@ -30,6 +30,63 @@ OUTBS_INT_FIELDS = ("cd", "tauw_n", "mss", "strn", "wefmag", "wefdir", "ctcor", 
 OUTBS_INT_GROUPS = dict(slopes=1, strain=2, flux=4, ctcor=8, bands=16, point=32)
 OUTBS_INT_ALL = 63
 
+# ---- OUTBLOCK's parameter table: this project's restatement of mpcrtbl.F90:92-469 as (number, short name, sea-ice mask, sea mask), the numbers from
+# the reference's index formulas (outblock.F90:437-604) with the NTRAIN and NTEWH the library is written for
+NTRAIN, NTEWH = 3, 6
+JPPFLAG = 75 + 3 * NTRAIN + 5
+
+
+def _outblock_params():
+    T, F = True, False
+    n3 = 3 * NTRAIN
+    rows = [(1, "swh", T, T), (2, "mwd", T, T), (3, "mwp", T, T), (4, "ufric", F, T), (5, "dwi", F, F), (6, "pp1d", T, T), (7, "cdww", F, F),
+            (8, "tauw_n", T, T), (9, "msqs", T, T), (10, "wind", F, F), (11, "shww", T, T), (12, "shts", T, T), (13, "mdww", T, T), (14, "mdts", T, T),
+            (15, "mpww", T, T), (16, "mpts", T, T), (17, "altwh", T, T), (18, "caltwh", T, T), (19, "raltcor", T, T), (20, "mp1", T, T),
+            (21, "mp2", T, T), (22, "wdw", T, T), (23, "p1ww", T, T), (24, "p1ps", T, T), (25, "p2ww", T, T), (26, "p2ps", T, T), (27, "dwww", T, T),
+            (28, "dwps", T, T), (29, "wsk", T, T), (30, "bfi", T, T), (31, "wsp", T, T), (32, "wmb", F, T), (33, "hmax", T, T), (34, "tmax", T, T),
+            (35, "ust", T, T), (36, "vst", T, T), (37, "ocu", F, T), (38, "vcu", F, T), (39, "phieps", F, T), (40, "phiaw", F, T), (41, "tauoc", F, T)]
+    for itr in range(1, NTRAIN + 1):
+        rows += [(42 + 3 * (itr - 1), f"swh{itr}", T, T), (43 + 3 * (itr - 1), f"mwd{itr}", T, T), (44 + 3 * (itr - 1), f"mwp{itr}", T, T)]
+    rows += [(42 + n3, "strn", F, T), (43 + n3, "h10", T, T), (44 + n3, "aird", F, F), (45 + n3, "wstar", F, F), (46 + n3, "ci", F, T),
+             (47 + n3, "cithick", F, T), (48 + n3, "c3", T, T), (49 + n3, "sic", F, F), (50 + n3, "nemocithick", F, F), (51 + n3, "ucurr", F, F),
+             (52 + n3, "vcurr", F, F), (53 + n3, "wefmag", T, T), (54 + n3, "wefdir", T, T)]
+    periods = (10, 12, 14, 17, 21, 25, 30)          # IPRMINFO(:,4:5) of the bands, mpcrtbl.F90:371-399
+    rows += [(54 + n3 + ih, f"h{periods[ih - 1]}{periods[ih]}", T, T) for ih in range(1, NTEWH + 1)]
+    b = n3 + NTEWH
+    rows += [(55 + b, "eta_m", T, T), (56 + b, "r", T, T), (57 + b, "xnslc", T, T), (58 + b, "tauxd", F, T), (59 + b, "tauyd", F, T),
+             (60 + b, "tauocxd", F, T), (61 + b, "tauocyd", F, T), (62 + b, "phiocd", F, T), (63 + b, "tdcmax", T, T), (64 + b, "tdhmax", T, T),
+             (65 + b, "stcmax", T, T), (66 + b, "sthmax", T, T), (67 + b, "sibm", T, T), (68 + b, "xwrs", T, T), (69 + b, "ywrs", T, T)]
+    # the five extra fields JPPFLAG-5+IC (mpcrtbl.F90:464-469); OUTBLOCK fills the first two "for testing" (outblock.F90:597-604)
+    extra = {70 + b: "ctcor", 71 + b: "mss_m"}
+    rows += [(JPPFLAG - 5 + ic, extra.get(JPPFLAG - 5 + ic, f"extra{JPPFLAG - 5 + ic:03d}"), F, F) for ic in range(1, 6)]
+    assert [r[0] for r in rows] == list(range(1, JPPFLAG + 1))
+    return tuple(rows)
+
+
+OUTBLOCK_PARAMS = _outblock_params()
+OUTBLOCK_NUMBER = {name: ir for ir, name, _, _ in OUTBLOCK_PARAMS}
+# the calls of a plan, in the bit order of ecwam_hip_outblock_plan
+OUTBLOCK_CALLS = ("outbs", "sepwisw", "partition", "extremes", "absolute", "second_order", "integrals")
+
+
+def outblock_tables(requested):
+    """(IPFGTBL, ITOBOUT, NIPRMOUT) of a request as mpcrtbl.F90:473-502 builds them: requested is an iterable of parameter numbers, or a mapping
+    parameter -> IPFGTBL value (any value /= 0 puts the parameter on the list; -1 is the reference's "normed only").  Columns are handed out in the
+    order of the parameter numbers."""
+    val = dict(requested) if hasattr(requested, "keys") else {int(ir): 1 for ir in requested}
+    for ir in val:
+        if not 1 <= int(ir) <= JPPFLAG:
+            raise ValueError(f"OUTBLOCK: parameter {ir} outside 1 .. {JPPFLAG}")
+    ipfgtbl = np.zeros(JPPFLAG, np.int32)
+    itobout = np.zeros(JPPFLAG, np.int32)
+    n = 0
+    for ir in range(1, JPPFLAG + 1):
+        if val.get(ir, 0) != 0:
+            ipfgtbl[ir - 1] = val[ir]
+            n += 1
+            itobout[ir - 1] = n
+    return ipfgtbl, itobout, n
+
 
 class EcwamHipError(RuntimeError):
     pass
@@ -454,6 +511,62 @@ class HipContext:
         pio = None if iodp is None else self._int(iodp, (iodp.shape[0],), "IODP")
         self._chk(self.lib.ecwam_hip_outsetwmask(self._h, kijs, kijl, out.data_ptr(), out.shape[1], cf.ctypes.data, pff, pio,
                                                  float(self.t.CITHRSH if cithrsh is None else cithrsh), float(zmiss), _stream_ptr()))
+
+    # -- OUTBLOCK as one call (ecwam_hip_set_outblock / ecwam_hip_outblock_plan / ecwam_hip_outblock)
+    def set_outblock(self, requested, itobout=None, niprmout=None, second_order: bool = False, small_domain: bool = False, llsource: bool = True):
+        """The request of outblock(): parameter numbers (or a mapping parameter -> IPFGTBL value).  itobout / niprmout: ITOBOUT(1:JPPFLAG) and the
+        number of columns when the host has its own; default: outblock_tables().  The masks are those of OUTBLOCK_PARAMS.  second_order:
+        LSECONDORDER; small_domain: CLDOMAIN = 's'; llsource = False: no sea-ice mask.  Returns {parameter: 0-based column}."""
+        ipf, ito, n = outblock_tables(requested)
+        if itobout is not None:
+            ito = np.ascontiguousarray(itobout, dtype=np.int32)
+            if ito.shape != (JPPFLAG,):
+                raise ValueError(f"OUTBLOCK: ITOBOUT has {JPPFLAG} entries")
+        n = n if niprmout is None else int(niprmout)
+        ice = np.ascontiguousarray([int(p[2]) for p in OUTBLOCK_PARAMS], dtype=np.int32)
+        sea = np.ascontiguousarray([int(p[3]) for p in OUTBLOCK_PARAMS], dtype=np.int32)
+        flags = (1 if second_order else 0) | (2 if small_domain else 0) | (0 if llsource else 4)
+        self._outblock = None      # a refused call leaves the previous plan in the library, but this layer forgets it
+        self._chk(self.lib.ecwam_hip_set_outblock(self._h, JPPFLAG, ipf.ctypes.data, ito.ctypes.data, ice.ctypes.data, sea.ctypes.data, n, flags))
+        self._outblock = dict(niprmout=n, columns={ir + 1: int(ito[ir]) - 1 for ir in range(JPPFLAG) if ipf[ir] != 0})
+        return dict(self._outblock["columns"])
+
+    def outblock_plan(self) -> dict:
+        """What outblock() will run: calls (names of OUTBLOCK_CALLS), int_groups (a sum of OUTBS_INT_GROUPS values), w_maxh, stores_fl2nd."""
+        calls, st = C.c_int(0), C.c_int(0)
+        self._chk(self.lib.ecwam_hip_outblock_plan(self._h, C.byref(calls), C.byref(st)))
+        m = int(calls.value)
+        return dict(calls=tuple(nm for i, nm in enumerate(OUTBLOCK_CALLS) if m >> i & 1), int_groups=(m >> 8) & 63, w_maxh=bool(m >> 14 & 1),
+                    stores_fl2nd=bool(st.value), mask=m)
+
+    def outblock(self, kijs, kijl, bout, fl1=None, xllws=None, mij=None, wvprpt=None, ff=None, intf=None, ucur=None, vcur=None, iodp=None, ibrmem=None,
+                 altim=None, nemo=None, cithrsh: float | None = None, zmiss: float = -999.0):
+        """Rows [kijs, kijl) of bout[:, NIPRMOUT] as OUTBLOCK fills them (ecwam_hip_outblock), for the request of set_outblock().  Operands no
+        requested parameter reads may be None.  altim: reals [3][>= kijl] (ALTWH, CALTWH, RALTCOR); nemo: float64 [4][>= kijl] (NEMOCICOVER,
+        NEMOCITHICK, NEMOUCUR, NEMOVCUR); ibrmem: reals [>= kijl]; iodp: int32 [>= kijl]."""
+        ob = getattr(self, "_outblock", None)
+        ncol = ob["niprmout"] if ob else bout.shape[1]      # without a plan the library refuses
+        opt = lambda a, shape, name: None if a is None else self._real(a, shape, name)
+        rows = [bout.shape[0]] + [a.shape[0] for a in (fl1, xllws, mij, wvprpt, ff, intf, ucur, vcur, iodp, ibrmem) if a is not None]
+        rows += [a.shape[1] for a in (altim, nemo) if a is not None]
+        if not (0 <= kijs <= kijl <= min(rows)):
+            raise ValueError("OUTBLOCK: KIJS/KIJL outside the operands")
+
+        def planes(a, k, dtype, name):       # the library takes planes of exactly kijl points
+            if a is None:
+                return None
+            if not (a.is_cuda and a.dtype == dtype and a.dim() == 2 and a.shape[0] == k):
+                raise ValueError(f"{name}: expected a {dtype} cuda tensor [{k}][>= KIJL]")
+            return a[:, :kijl].contiguous()
+        pa, pn = planes(altim, 3, self.dtype, "ALTIM"), planes(nemo, 4, torch.float64, "NEMO")
+        r0 = lambda a: 0 if a is None else a.shape[0]
+        args = [opt(fl1, (r0(fl1), self.NANG, self.NFRE), "FL1"), opt(xllws, (r0(xllws), self.NANG, self.NFRE), "XLLWS"),
+                None if mij is None else self._int(mij, (mij.shape[0],), "MIJ"), opt(wvprpt, (r0(wvprpt), NWPR, self.NFRE), "WVPRPT"),
+                opt(ff, (r0(ff), NFF), "FF"), opt(intf, (r0(intf), NINTF), "INTF"), opt(ucur, (r0(ucur),), "UCUR"), opt(vcur, (r0(vcur),), "VCUR"),
+                None if iodp is None else self._int(iodp, (iodp.shape[0],), "IODP"), opt(ibrmem, (r0(ibrmem),), "IBRMEM"),
+                None if pa is None else pa.data_ptr(), None if pn is None else pn.data_ptr()]
+        self._chk(self.lib.ecwam_hip_outblock(self._h, kijs, kijl, *args, float(self.t.CITHRSH if cithrsh is None else cithrsh), float(zmiss),
+                                              self._real(bout, (bout.shape[0], ncol), "BOUT"), _stream_ptr()))
 
     def outwnorm(self, field, column: int, n: int, zmiss: float = -999.0):
         """(average, minimum, maximum, count) of field[:n, column] over the values != zmiss."""

@@ -82,6 +82,13 @@ struct ecwam_hip_ctx {
   // ecwam_hip_set_outbs_integrals (csrc/outbs_int.hip): IntTab<T> in device memory; the number of bands, -1 before the setter is called
   void* int_tab = nullptr;
   int int_nband = -1;
+  std::vector<double> int_tb, int_tt;   // the bands as passed: ecwam_hip_set_outblock compares them with the period intervals of the request
+  // ecwam_hip_set_outblock (csrc/outblock.hip): the plan, its per-column descriptors on the device, the work space of ecwam_hip_outblock
+  OutblockPlan ob_plan;
+  bool ob_set = false;
+  int* ob_desc = nullptr;
+  void* ob_work = nullptr;
+  size_t ob_work_bytes = 0;
   const void* obs = nullptr;  // LSUBGRID: device OBS[n_obs][8][NFRE] (ecwam_hip_set_obstructions), read by CTUW / PROPAGS2
   int n_obs = 0;
 };
@@ -508,6 +515,8 @@ int ecwam_hip_destroy(ecwam_hip_ctx* c) {
   if (c->so_coef) (void)hipFree(c->so_coef);
   if (c->so_work) (void)hipFree(c->so_work);
   if (c->int_tab) (void)hipFree(c->int_tab);
+  if (c->ob_desc) (void)hipFree(c->ob_desc);
+  if (c->ob_work) (void)hipFree(c->ob_work);
   if (c->fin) (void)hipFree(c->fin);
   if (c->wi) (void)hipFree(c->wi);
   if (c->adv_pt) (void)hipFree(c->adv_pt);
@@ -994,6 +1003,8 @@ int ecwam_hip_set_outbs_integrals(ecwam_hip_ctx* c, double xkmss_cutoff, int nba
   if (!c->int_tab) HIPCHK(hipMalloc(&c->int_tab, h.size()));
   HIPCHK(hipMemcpy(c->int_tab, h.data(), h.size(), hipMemcpyHostToDevice));
   c->int_nband = nband;
+  c->int_tb.clear(); c->int_tt.clear();
+  if (nband) { c->int_tb.assign(tb, tb + nband); c->int_tt.assign(tt, tt + nband); }
   return 0;
 }
 
@@ -1031,6 +1042,98 @@ int ecwam_hip_outsetwmask(ecwam_hip_ctx* c, int kijs, int kijl, void* out, int n
   if (kijl > kijs && (any & 2) && !iodp) return fail("ecwam_hip_outsetwmask: a column has the sea mask but iodp is NULL");
   if (kijl > kijs && ice && (any & 1) && !ff) return fail("ecwam_hip_outsetwmask: the sea-ice mask needs ff (CICOVER)");
   in_precision(c, [&](auto t) { launch_outsetwmask<decltype(t)>(kijs, kijl, out, ncol, cols, ff, iodp, ice, cithrsh, zmiss, (hipStream_t)stream); });
+  return launched();
+}
+
+int ecwam_hip_set_outblock(ecwam_hip_ctx* c, int jppflag, const int* ipfgtbl, const int* itobout, const int* icemask, const int* seamask, int niprmout, int flags) {
+  if (!c) return fail("null context");
+  double fr1 = 0.0;
+  in_precision(c, [&](auto t) { fr1 = (double)((const decltype(t)*)c->fr_host.data())[0]; });
+  const OutblockCtx oc{c->NANG, c->NFRE, c->real_bytes, c->p.irefra, c->p.licerun, c->p.lmaskice, c->p.lwnemocoustrn, c->so_tab && c->so_coef, c->itab != nullptr,
+                       c->int_nband, c->int_tb.data(), c->int_tt.data(), fr1};
+  OutblockPlan plan;
+  const std::string why = outblock_plan_build(oc, jppflag, ipfgtbl, itobout, icemask, seamask, niprmout, flags, plan);
+  if (!why.empty()) return fail("ecwam_hip_set_outblock: " + why);
+  HIPCHK(hipSetDevice(c->device));
+  HIPCHK(hipDeviceSynchronize());   // no call in flight reads the descriptors that are replaced
+  c->ob_set = false;
+  if (c->ob_desc) (void)hipFree(c->ob_desc);
+  c->ob_desc = nullptr;
+  HIPCHK(hipMalloc(&c->ob_desc, plan.desc.size() * sizeof(int)));
+  HIPCHK(hipMemcpy(c->ob_desc, plan.desc.data(), plan.desc.size() * sizeof(int), hipMemcpyHostToDevice));
+  c->ob_plan = plan;
+  c->ob_set = true;
+  return 0;
+}
+
+int ecwam_hip_outblock_plan(ecwam_hip_ctx* c, int* calls, int* stores_fl2nd) {
+  if (!c) return fail("null context");
+  if (!c->ob_set) return fail("ecwam_hip_outblock_plan: no plan (ecwam_hip_set_outblock)");
+  if (calls) *calls = c->ob_plan.calls | (c->ob_plan.int_groups << 8) | (c->ob_plan.ext_full << 14);
+  if (stores_fl2nd) *stores_fl2nd = c->ob_plan.stores_fl2nd;
+  return 0;
+}
+
+int ecwam_hip_outblock(ecwam_hip_ctx* c, int kijs, int kijl, const void* fl1, const void* xllws, const int* mij, const void* wvprpt, const void* ff, const void* intf,
+                       const void* ucur, const void* vcur, const int* iodp, const void* ibrmem, const void* altim, const double* nemo, double cithrsh, double zmiss,
+                       void* bout, void* stream) {
+  if (outbs_head(c, kijs, kijl, "ecwam_hip_outblock: bad range")) return 1;
+  if (!c->ob_set) return fail("ecwam_hip_outblock: no plan: call ecwam_hip_set_outblock first");
+  const OutblockPlan& P = c->ob_plan;
+  if (kijl == kijs) return 0;
+  if (!bout) return fail("ecwam_hip_outblock: bout is NULL");
+  {   // every array the plan reads, before anything is launched
+    static const char* const name[12] = {"fl1", "xllws", "mij", "wvprpt", "ff", "intf", "ucur", "vcur", "iodp", "ibrmem", "altim", "nemo"};
+    const void* const ptr[12] = {fl1, xllws, mij, wvprpt, ff, intf, ucur, vcur, iodp, ibrmem, altim, nemo};
+    for (int b = 0; b < 12; b++)
+      if ((P.need >> b & 1) && !ptr[b])
+        return fail(std::string("ecwam_hip_outblock: ") + name[b] + " is NULL but parameter " + std::to_string(P.why_param[b]) + " is requested and reads it");
+  }
+  // the state the plan was derived from must still be there
+  if ((P.calls & OB_CALL_SECOND_ORDER) && (!c->so_tab || !c->so_coef)) return fail("ecwam_hip_outblock: the second-order tables were removed after ecwam_hip_set_outblock");
+  if ((P.calls & OB_CALL_INTEGRALS) && c->int_nband < 0) return fail("ecwam_hip_outblock: ecwam_hip_set_outbs_integrals not called");
+  if ((P.int_groups & 16) && c->int_nband != 7) return fail("ecwam_hip_outblock: the bands were changed after ecwam_hip_set_outblock");
+  hipStream_t s = (hipStream_t)stream;
+  // work space: the packed rows of the calls, indexed by the absolute row as they write them; DEPTH for the second-order call; FL2ND when the bands read it
+  const size_t rb = (size_t)c->real_bytes, n = (size_t)kijl;
+  const int wint = 8 + (c->int_nband > 0 ? c->int_nband : 0);
+  auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  const size_t o8 = 0, osep = o8 + up(n * 8 * rb), oext = osep + up(n * 24 * rb), oint = oext + up(n * 13 * rb), odep = oint + up(n * wint * rb),
+               ofl = odep + ((P.calls & OB_CALL_SECOND_ORDER) ? up(n * rb) : 0), need = ofl + (P.stores_fl2nd ? up(n * c->NANG * c->NFRE * rb) : 0);
+  if (need > c->ob_work_bytes) {
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipDeviceSynchronize());
+    if (c->ob_work) (void)hipFree(c->ob_work);
+    c->ob_work = nullptr; c->ob_work_bytes = 0;
+    HIPCHK(hipMalloc(&c->ob_work, need));
+    c->ob_work_bytes = need;
+  }
+  char* w = (char*)c->ob_work;
+  void *w8 = w + o8, *wsep = w + osep, *wext = w + oext, *wi = w + oint, *wdep = w + odep, *wfl = P.stores_fl2nd ? w + ofl : nullptr;
+  if (P.calls & OB_CALL_OUTBS)
+    if (ecwam_hip_outbs(c, kijs, kijl, fl1, zmiss, w8, stream)) return 1;
+  if (P.calls & OB_CALL_ABSOLUTE)
+    if (ecwam_hip_outbs_absolute(c, kijs, kijl, fl1, wvprpt, ucur, vcur, ff, 0, zmiss, w8, wfl, stream)) return 1;
+  if (P.calls & OB_CALL_SECOND_ORDER) {
+    in_precision(c, [&](auto t) { launch_outblock_depth<decltype(t)>(kijs, kijl, ff, wdep, s); });
+    if (ecwam_hip_outbs_second_order(c, kijs, kijl, fl1, wvprpt, wdep, ucur, vcur, ff, 1.0, zmiss, w8, wfl, stream)) return 1;
+  }
+  if (P.calls & OB_CALL_SEPWISW)
+    if (ecwam_hip_outbs_sepwisw(c, kijs, kijl, fl1, xllws, wvprpt, ff, (P.flags & 2) ? 1 : 0, zmiss, wsep, stream)) return 1;
+  if (P.calls & OB_CALL_PARTITION)
+    if (ecwam_hip_outbs_partition(c, kijs, kijl, fl1, xllws, mij, wvprpt, ff, 0, zmiss, wsep, stream)) return 1;
+  if (P.calls & OB_CALL_EXTREMES)
+    if (ecwam_hip_outbs_extremes(c, kijs, kijl, fl1, wvprpt, ff, P.ext_full ? 0 : 1, wext, stream)) return 1;
+  if (P.calls & OB_CALL_INTEGRALS)
+    if (ecwam_hip_outbs_integrals(c, kijs, kijl, fl1, wfl, wvprpt, ff, P.int_groups, zmiss, wi, stream)) return 1;
+  OutblockSrc src;
+  for (int i = 0; i < OB_NSRC; i++) { src.base[i] = nullptr; src.pstride[i] = 0; src.cstride[i] = 0; }
+  auto rows = [&](int i, const void* b, int width) { src.base[i] = b; src.pstride[i] = width; src.cstride[i] = 1; };
+  auto planes = [&](int i, const void* b) { src.base[i] = b; src.pstride[i] = 1; src.cstride[i] = kijl; };
+  rows(OB_W8, w8, P.w8_stride); rows(OB_SEP, wsep, P.sep_stride); rows(OB_EXT, wext, 13); rows(OB_INT, wi, wint);
+  rows(OB_FF, ff, ECWAM_HIP_NFF); rows(OB_INTF, intf, ECWAM_HIP_NINTF); rows(OB_UCUR, ucur, 1); rows(OB_VCUR, vcur, 1); rows(OB_IBRMEM, ibrmem, 1);
+  planes(OB_ALTIM, altim); planes(OB_NEMO, nemo);
+  in_precision(c, [&](auto t) { launch_outblock_assemble<decltype(t)>(kijs, kijl, P.niprmout, c->ob_desc, src, ff, iodp, P.ice, P.sea, P.need_ci, cithrsh, zmiss, bout, s); });
   return launched();
 }
 

@@ -3,6 +3,7 @@
 // spell these signatures, so a definition that drifts from its declaration does not compile.
 #pragma once
 #include <cstddef>
+#include <string>
 #include <vector>
 
 #include <hip/hip_runtime.h>
@@ -90,3 +91,39 @@ const char* so_tab_build(const ecwam_hip_params* p, const void* fr, int real_byt
         std::vector<unsigned char>& host);
 void so_coef_layout(int real_bytes, int ND, int AH, int NH, const void* const src[5], std::vector<unsigned char>& host);
 size_t so_work_bytes(int real_bytes, int n, int AH, int NH, int NMAX);
+
+// ---- outblock.hip: OUTBLOCK itself (outblock.F90:159-610) -- the plan of ecwam_hip_set_outblock and the kernel that fills BOUT ---------------------
+// where a BOUT column comes from: the packed buffers of the output calls (in the work space of the context), the caller's per-point arrays, or nothing
+enum { OB_ZERO = 0, OB_W8, OB_SEP, OB_EXT, OB_INT, OB_FF, OB_INTF, OB_UCUR, OB_VCUR, OB_IBRMEM, OB_ALTIM, OB_NEMO, OB_NSRC };
+// what is done to the value: copy; MOD(DEG*x+180,360); MAX(-x,0); IBRMEMOUT's rule (zmiss where not CICOVER > 0).  OB_NEMO columns hold doubles.
+enum { OB_COPY = 0, OB_DEG, OB_NEGMAX, OB_IBR };
+// the calls of a plan (the bit mask ecwam_hip_outblock_plan returns; bits 8-13: the group flags of ecwam_hip_outbs_integrals, bit 14: W_MAXH runs)
+enum { OB_CALL_OUTBS = 1, OB_CALL_SEPWISW = 2, OB_CALL_PARTITION = 4, OB_CALL_EXTREMES = 8, OB_CALL_ABSOLUTE = 16, OB_CALL_SECOND_ORDER = 32, OB_CALL_INTEGRALS = 64 };
+// the caller's arrays a plan reads
+enum { OB_NEED_FL1 = 1, OB_NEED_XLLWS = 2, OB_NEED_MIJ = 4, OB_NEED_WVPRPT = 8, OB_NEED_FF = 16, OB_NEED_INTF = 32, OB_NEED_UCUR = 64, OB_NEED_VCUR = 128,
+       OB_NEED_IODP = 256, OB_NEED_IBRMEM = 512, OB_NEED_ALTIM = 1024, OB_NEED_NEMO = 2048 };
+struct OutblockPlan {
+  int niprmout = 0;
+  int calls = 0, int_groups = 0, ext_full = 0, stores_fl2nd = 0;
+  int w8_stride = 5, sep_stride = 15;   // ecwam_hip_outbs / _absolute rows, ecwam_hip_outbs_sepwisw / _partition rows
+  int flags = 0;                        // as passed to ecwam_hip_set_outblock
+  int ice = 0, sea = 0, need_ci = 0;    // the sea-ice mask applies to some column; the sea mask does; CICOVER is read (either mask or IBRMEMOUT)
+  unsigned need = 0;                    // OB_NEED_*
+  int why_param[12] = {0};              // per OB_NEED_* bit: one requested parameter that reads the array (for the refusal's text)
+  std::vector<int> desc;                // [niprmout][2]: source | op << 8 | mask bits << 16, source column
+};
+// what ecwam_hip_set_outblock needs of the context
+struct OutblockCtx {
+  int NANG, NFRE, real_bytes, irefra, licerun, lmaskice, lwnemocoustrn;
+  int has_second_order, has_itab, int_nband;
+  const double *int_tb, *int_tt;        // the bands of ecwam_hip_set_outbs_integrals
+  double fr1;                           // FR(1)
+};
+// a refusal's reason, or the empty string
+std::string outblock_plan_build(const OutblockCtx& c, int jppflag, const int* ipfgtbl, const int* itobout, const int* icemask, const int* seamask, int niprmout,
+        int flags, OutblockPlan& plan);
+// element (ij, col) of source s at base[s] + ij * pstride[s] + col * cstride[s] (in elements of the source: reals, doubles for OB_NEMO)
+struct OutblockSrc { const void* base[OB_NSRC]; long long pstride[OB_NSRC], cstride[OB_NSRC]; };
+template <typename T> void launch_outblock_assemble(int kijs, int kijl, int ncol, const int* desc, const OutblockSrc& src, const void* ff, const int* iodp, int ice, int sea,
+        int need_ci, double cithrsh, double zmiss, void* bout, hipStream_t s);
+template <typename T> void launch_outblock_depth(int kijs, int kijl, const void* ff, void* depth, hipStream_t s);   // depth[ij] = ff[ij][15]

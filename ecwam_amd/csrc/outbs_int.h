@@ -1,5 +1,5 @@
 // The constants of k_outbs_integrals (csrc/outbs_int.hip) that ecwam_hip_set_outbs_integrals works out once, in the working precision T:
-// the two mean-square-slope cut-offs of OUTBLOCK (0: XKMSS_CUTOFF, parameter 9; 1: (ZPI FR(NFRE))**2 / G, parameter 83), SEBTMEAN's
+// the two mean-square-slope cut-offs of OUTBLOCK (0: XKMSS_CUTOFF, parameter 9; 1: (ZPI FR(NFRE))**2 / G, parameter 86), SEBTMEAN's
 // per-band constants (sebtmean.F90:81-102, 119-120, 148-149, 165, 172-175, 184) and DELKCC_GC, the one gravity-capillary table DevTab
 // does not hold on its own.  One instance per context in device memory.
 #pragma once

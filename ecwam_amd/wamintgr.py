@@ -639,6 +639,33 @@ class Wamintgr:
         self.ctx.outbs_integrals(0, self.n, self.fl1, self.wvprpt, self.ff, out, fl2nd=fl2nd, groups=groups)
         return out
 
+    # ---- OUTBLOCK as one device call: (bout [n][NIPRMOUT], {parameter: column}).  requested: parameter numbers of api.OUTBLOCK_PARAMS; default:
+    # every parameter whose inputs this driver holds -- no altimeter data (17-19), no NEMO fields (58-61), currents (37, 38) only with IREFRA = 2 / 3.
+    # ITOBOUT as mpcrtbl.F90:473-502 builds it; every point is deep enough (IODP = 1); IBRMEM is the input slot of the INTF rows.  The integrals'
+    # bands and the second-order tables are set on first use, as in outbs_integrals() / outbs_second_order().
+    def outblock(self, requested=None, second_order: bool = False):
+        cur = self.irefra >= 2
+        if requested is None:
+            requested = [p[0] for p in api.OUTBLOCK_PARAMS if not (17 <= p[0] <= 19 or 58 <= p[0] <= 61 or (p[0] in (37, 38) and not cur))]
+        requested = sorted(set(int(r) for r in requested))
+        if self.ctx.integral_bands is None:
+            self.ctx.set_outbs_integrals()
+        if second_order and not self.ctx.has_second_order:
+            from .second_order import SecondOrderTables
+            self.second_order_tables = SecondOrderTables(self.t)
+            self.ctx.set_second_order(self.second_order_tables)
+        key = (tuple(requested), bool(second_order))
+        if getattr(self, "_outblock_key", None) != key:
+            self._outblock_key = None
+            self._outblock_columns = self.ctx.set_outblock(requested, second_order=second_order)
+            self._outblock_key = key
+        bout = torch.zeros((self.n, len(requested)), dtype=self.dtype, device=self.dev)
+        u, v = (self.u_ext, self.v_ext) if cur else (None, None)
+        iodp = torch.ones(self.n, dtype=torch.int32, device=self.dev)
+        self.ctx.outblock(0, self.n, bout, fl1=self.fl1, xllws=self.xllws, mij=self.mij, wvprpt=self.wvprpt, ff=self.ff, intf=self.intf, ucur=u, vcur=v,
+                          iodp=iodp, ibrmem=self.intf[:, 15].contiguous())
+        return bout, dict(self._outblock_columns)
+
     def swh_norm(self):
         return self.ctx.outwnorm(self.outbs(), 0, self.n)
 

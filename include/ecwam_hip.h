@@ -454,7 +454,7 @@ int ecwam_hip_outbs_second_order(ecwam_hip_ctx *ctx, int kijs, int kijl, const v
  * The constants of ecwam_hip_outbs_integrals, worked out once in the working precision and kept on the device.  Host arrays are copied
  * before the call returns.
  *   xkmss_cutoff   XKMSS_CUTOFF of YOWFRED, the wavenumber up to which parameter 9 integrates the slope; <= 0 selects XK_GC(NWAV_GC) as
- *                  userin.F90:1214 does.  The second cut-off, (ZPI FR(NFRE))**2 / G of parameter 83 (outblock.F90:602), needs no argument.
+ *                  userin.F90:1214 does.  The second cut-off, (ZPI FR(NFRE))**2 / G of parameter 86 (outblock.F90:602), needs no argument.
  *   nband, tb, tt  0 .. 8 period bands as SEBTMEAN's arguments: tb[i] the shorter and tt[i] the longer period [s] of band i (host doubles,
  *                  rounded to the working precision).  The reference's seven: (10, 1/FR(1)) = SE10MEAN, then (10,12) (12,14) (14,17) (17,21)
  *                  (21,25) (25,30) (outblock.F90:460, 515-519).  Per band the library precomputes MCUTB, MCUTT, FRLOC, the interpolation
@@ -481,7 +481,7 @@ int ecwam_hip_set_outbs_integrals(ecwam_hip_ctx *ctx, double xkmss_cutoff, int n
  *    2 mss    mean square slope up to XKMSS_CUTOFF [9]     3 strn    mean square strain in the ice, CIMSSTRN [51]; with LWNEMOCOUSTRN the
  *                                                                    reference outputs STRNMS of INTF instead: the host's choice
  *    4 wefmag wave energy flux magnitude [62]              5 wefdir  its direction, MOD(DEG*WEFDIR+180,360) [63]
- *    6 ctcor  crest-trough correlation or zmiss [82]       7 mss_m   mean square slope up to (ZPI FR(NFRE))**2 / G [83]
+ *    6 ctcor  crest-trough correlation or zmiss [85]       7 mss_m   mean square slope up to (ZPI FR(NFRE))**2 / G [86]
  *    8 + i    4*SQRT(MAX(E,0)) of band i [52, 64-69 with the seven bands above]
  * flags: the column groups to compute, so that a host pays only for what IPFGTBL asks -- 1 slopes (2, 7), 2 strain (3), 4 flux (4, 5),
  * 8 CTCOR (6), 16 bands (8 ...), 32 point-wise (0, 1).  Columns of unselected groups are not written; a group's columns are the same bits
@@ -509,6 +509,63 @@ int ecwam_hip_outbs_integrals(ecwam_hip_ctx *ctx, int kijs, int kijl, const void
  */
 int ecwam_hip_outsetwmask(ecwam_hip_ctx *ctx, int kijs, int kijl, void *out, int ncol, const int *colflags, const void *ff, const int *iodp,
                           double cithrsh, double zmiss, void *stream);
+
+/*
+ * OUTBLOCK itself (outblock.F90:159-610; the routine the reference's GPU build runs on the device, outbs_loki_gpu.F90:104-125): one call that
+ * works out what a request needs, runs only that, and fills BOUT(KIJL, NIPRMOUT) -- every value in its column ITOBOUT(IR), masked by OUTSETWMASK.
+ *
+ * ecwam_hip_set_outblock: the request.  All pointers are HOST int[jppflag], copied before the call returns; entry IR-1 belongs to parameter IR of
+ * mpcrtbl.F90:92-469 (with NTRAIN = 3, NTEWH = 6: 42 + 3 (ITR-1) the swell trains, 51 the strain, 52 SE10MEAN, 62 / 63 the energy flux, 63 + IH the
+ * bands, 70-72, 78-81, 82 IBRMEMOUT, 83 / 84 TAUICX / TAUICY, 85 CTCOR, 86 the mean square slope up to the model's cut-off, 87-89 unused extra fields).
+ *   ipfgtbl   IPFGTBL: /= 0 -- the parameter is requested (-1, a parameter that is only normed, counts as in the reference)
+ *   itobout   ITOBOUT: the 1-based column of the parameter in BOUT, or 0
+ *   icemask, seamask   IPRMINFO(IR,6), IPRMINFO(IR,7): 1 -- the sea-ice mask / the sea mask applies
+ *   niprmout  NIPRMOUT, the number of columns of BOUT (<= 128); a column no requested parameter is mapped to is written as 0
+ *   flags     bit 0 LSECONDORDER; bit 1 CLDOMAIN = 's'; bit 2 LLSOURCE = F: no sea-ice mask (outsetwmask.F90:60)
+ *   jppflag   must be 89 = 75 + 3 NTRAIN + 5: the library is written for NTRAIN = 3; NTEWH = 6 comes with the seven bands of
+ *             ecwam_hip_set_outbs_integrals, which must be set before this call when a parameter of ecwam_hip_outbs_integrals is requested
+ * The call derives a plan and keeps it on the context: which of the output calls above run and with which group flags (so that only what a
+ * requested column reads is computed), whether FL2ND is stored, and one descriptor per column of BOUT (source buffer, source column, operation, mask
+ * bits) on the device.  The output spectrum is built once, as params.irefra / licerun / lmaskice and bit 0 select: with FL2ND = FL1 parameters 1, 2,
+ * 3, 6 come from ecwam_hip_outbs and 20-22 from ecwam_hip_outbs_sepwisw / _partition; else they come from ecwam_hip_outbs_absolute or
+ * ecwam_hip_outbs_second_order, and the spectrum is stored only when a band (52, 64-69) is requested.  11-16 and 23-28 come from
+ * ecwam_hip_outbs_partition when one of 42-50 is requested (LLPARTITION, mpcrtbl.F90:535-543), else from ecwam_hip_outbs_sepwisw;
+ * ecwam_hip_outbs_extremes runs KURTOSIS only unless one of 78-81 is requested; with LWNEMOCOUSTRN parameter 51 is STRNMS of INTF and the strain
+ * group does not run (outblock.F90:451-457).
+ * Refused with a reason: jppflag /= 89; a requested parameter whose column is outside 1 .. niprmout; two parameters in one column; one of 42-50 with
+ * bit 1 (ecwam_hip_outbs_partition refuses that branch); a band requested while the bands of the context are not (10, 1/FR(1)), (10,12), (12,14),
+ * (14,17), (17,21), (21,25), (25,30) s; a parameter of ecwam_hip_outbs_integrals before ecwam_hip_set_outbs_integrals; bit 0 without second-order
+ * tables; a spectral size or NANG a needed call has no build for; unknown flags.  Synchronises the device; not thread safe against calls in flight.
+ *
+ * ecwam_hip_outblock_plan: *calls = bit 0 ecwam_hip_outbs, 1 _sepwisw, 2 _partition, 3 _extremes, 4 _absolute, 5 _second_order, 6 _integrals;
+ * bits 8-13 the group flags ecwam_hip_outbs_integrals runs with; bit 14 W_MAXH runs in ecwam_hip_outbs_extremes.  *stores_fl2nd: FL2ND goes to the
+ * work space.  Either pointer may be NULL.
+ *
+ * ecwam_hip_outblock: rows [kijs,kijl) of bout[npts][niprmout] (device reals, indexed by the absolute row, row-major like every output buffer here),
+ * each written exactly once.  Inputs as the calls above take them (fl1, xllws, mij, wvprpt, ff, ucur / vcur) plus
+ *   intf     INTF[ij][16]: 35 / 36 USTOKES / VSTOKES, 39-41 PHIEPS, PHIAW, TAUOC, 51 STRNMS (LWNEMOCOUSTRN), 73-76 TAUXD TAUYD TAUOCXD TAUOCYD,
+ *            77 MAX(-PHIOCD, 0), 83 / 84 TAUICX / TAUICY
+ *   iodp     device int[>= kijl], for the sea mask
+ *   ibrmem   device reals [>= kijl]: IBRMEM; 82 is IBRMEMOUT: ibrmem, or zmiss where not CICOVER > 0 (ibrmemout.F90:74-82)
+ *   altim    device reals [3][kijl]: ALTWH, CALTWH, RALTCOR (17-19); plane p of point ij at altim[p * kijl + ij]
+ *   nemo     device DOUBLE [4][kijl] (JWRO): NEMOCICOVER, NEMOCITHICK, NEMOUCUR, NEMOVCUR (58-61), rounded to the working precision on write;
+ *            planes as altim
+ * and from ff: 4 UFRIC, 5 MOD(DEG*WDWAVE+180,360), 10 WSWAVE, 32 DEPTH (ff[ij][15] everywhere; staged contiguously for ecwam_hip_outbs_second_order),
+ * 53 AIRD, 54 WSTAR, 55 CICOVER, 56 CITHICK.  Requested parameters no statement of OUTBLOCK fills (87-89) are 0.  Last comes OUTSETWMASK with each
+ * column's own bits, the sea-ice mask first, both as ecwam_hip_outsetwmask applies them (cithrsh, zmiss as there).
+ * A pointer may be NULL when no requested parameter reads it; a NULL pointer the plan reads is refused by name before anything is launched, as is
+ * a call before ecwam_hip_set_outblock.
+ * Work space: the packed rows of the calls (8 + 24 + 13 + 8 + nband reals per point), DEPTH for the second-order call and FL2ND [kijl][NANG][NFRE]
+ * when the bands read it live in a work space on the context, sized by kijl and grown on demand (a synchronising allocation on the first call and
+ * when kijl grows).  It is one per context: calls of this function on one context must be ordered on one stream (or separated by a
+ * synchronisation) -- the rule of ecwam_hip_outbs_second_order, whose work space this call uses as well.
+ */
+int ecwam_hip_set_outblock(ecwam_hip_ctx *ctx, int jppflag, const int *ipfgtbl, const int *itobout, const int *icemask, const int *seamask,
+                           int niprmout, int flags);
+int ecwam_hip_outblock_plan(ecwam_hip_ctx *ctx, int *calls, int *stores_fl2nd);
+int ecwam_hip_outblock(ecwam_hip_ctx *ctx, int kijs, int kijl, const void *fl1, const void *xllws, const int *mij, const void *wvprpt, const void *ff,
+                       const void *intf, const void *ucur, const void *vcur, const int *iodp, const void *ibrmem, const void *altim,
+                       const double *nemo, double cithrsh, double zmiss, void *bout, void *stream);
 
 /* NEWWIND forcing hand-over (newwind.F90:126-161): FF <- FF_NEXT members + TAUW cap.  ecwam_hip_newwind takes ICODE_WND = ICODE
  * of the parameters; a coupled host (LWCOU) passes ICODE_CPL through ecwam_hip_newwind_icode (newwind.F90:120-124). */
