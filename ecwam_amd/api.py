@@ -305,6 +305,35 @@ class HipContext:
             pw = wam2nemo.data_ptr()
         self._chk(self.lib.ecwam_hip_implsch(self._h, kijs, kijl, *a, pw, pd, _stream_ptr()))
 
+    # -- WDFLUXES (wdfluxes.F90:156-306) and SETICE (setice.F90:67-86): what OUTSTEP0 runs before the output of step 0
+    def wdfluxes_supported(self) -> bool:
+        """The flux-only mode covers the context's configuration (the common and the alternate builds of the IMPLSCH kernel)."""
+        return bool(self.lib.ecwam_hip_wdfluxes_supported(self._h))
+
+    def wdfluxes(self, kijs, kijl, fl1, wvprpt, ff, intf, mij, xllws, wam2nemo=None):
+        """FL1, WVPRPT and FF are read only; MIJ and XLLWS are written, and with LWFLUX / LWFLUXOUT the flux members of INTF (and columns
+        0, 1 of WAM2NEMO when LWNEMOCOU)."""
+        nrow = fl1.shape[0]
+        if not (0 <= kijs <= kijl <= min(nrow, wvprpt.shape[0], ff.shape[0], intf.shape[0], mij.shape[0], xllws.shape[0])):
+            raise ValueError("WDFLUXES: KIJS/KIJL outside the operands")
+        a = [self._real(fl1, (nrow, self.NANG, self.NFRE), "FL1"), self._real(wvprpt, (wvprpt.shape[0], NWPR, self.NFRE), "WVPRPT"),
+             self._real(ff, (ff.shape[0], NFF), "FF"), self._real(intf, (intf.shape[0], NINTF), "INTF"),
+             self._int(mij, (mij.shape[0],), "MIJ"), self._real(xllws, (xllws.shape[0], self.NANG, self.NFRE), "XLLWS")]
+        pw = None
+        if wam2nemo is not None:
+            if not (wam2nemo.is_cuda and wam2nemo.dtype == torch.float64 and wam2nemo.is_contiguous() and wam2nemo.dim() == 2
+                    and wam2nemo.shape[1] == 13 and wam2nemo.shape[0] >= kijl):
+                raise ValueError("WAM2NEMO: expected contiguous float64 cuda tensor [npts >= KIJL][13]")
+            pw = wam2nemo.data_ptr()
+        self._chk(self.lib.ecwam_hip_wdfluxes(self._h, kijs, kijl, *a, pw, _stream_ptr()))
+
+    def setice(self, kijs, kijl, fl1, ff):
+        nrow = fl1.shape[0]
+        if not (0 <= kijs <= kijl <= min(nrow, ff.shape[0])):
+            raise ValueError("SETICE: KIJS/KIJL outside the operands")
+        self._chk(self.lib.ecwam_hip_setice(self._h, kijs, kijl, self._real(fl1, (nrow, self.NANG, self.NFRE), "FL1"),
+                                            self._real(ff, (ff.shape[0], NFF), "FF"), _stream_ptr()))
+
     # -- the one-kernel step: PROPAGS2 inside IMPLSCH's tile load (ecwam_hip_propags2_implsch)
     def fused_supported(self, fast_waves: bool = False, obstructions: bool = False) -> bool:
         """The one-kernel step covers the context (and, if asked, its forms with fast-wave sub-steps / sub-grid obstructions)."""

@@ -137,7 +137,7 @@ static int build_tab(const ecwam_hip_params* p, const ecwam_hip_tables* t, DevTa
   d->LLGCBZ0 = p->llgcbz0; d->LLNORMAGAM = p->llnormagam; d->LLCAPCHNK = p->llcapchnk; d->LBIWBK = p->lbiwbk;
   d->LICERUN = p->licerun; d->LMASKICE = p->lmaskice; d->LWAMRSETCI = p->lwamrsetci; d->LWVFLX_SNL = p->lwvflx_snl;
   d->LWFLUX = p->lwflux; d->LCFLX = (p->lwflux || p->lwfluxout || p->lwnemocou); d->LWNEMOCOU = p->lwnemocou; d->LWCOU = p->lwcou;
-  d->LWCOUAST = p->lwcouast; d->LWNEMOCOUWRS = p->lwnemocouwrs;
+  d->LWCOUAST = p->lwcouast; d->LWNEMOCOUWRS = p->lwnemocouwrs; d->LCFLX_WD = (p->lwflux || p->lwfluxout);
   d->LWNEMOTAUOC = p->lwnemotauoc; d->LWNEMOCOUSEND = p->lwnemocousend; d->LWNEMOCOUSTK = p->lwnemocoustk;
   d->ICODE = p->icode; d->ISNONLIN = p->isnonlin; d->IPHYS = p->iphys; d->IDAMPING = p->idamping;
   d->LCISCAL = p->lciscal; d->LCIWA2 = p->lciwa2; d->LCIWA3 = p->lciwa3;
@@ -802,6 +802,58 @@ int ecwam_hip_implsch(ecwam_hip_ctx* c, int kijs, int kijl, void* fl1, const voi
   });
   if (rc == 0) { HIPCHK(hipGetLastError()); c->implsch_last = 4; return 0; }
   return fail("ecwam_hip_implsch: no build of k_implsch4 covers the configuration (ecwam_hip_create should have refused it)");
+}
+
+// WDFLUXES: the switch of a RARE configuration that keeps it from this call (the common and the alternate builds have the mode), or NULL
+static const char* wdfluxes_uncovered(const ecwam_hip_ctx* c) {
+  // (the double precision build at 24 directions computed wrong fluxes on the device: implsch4w.hip does not instantiate it)
+#ifndef ECWAM_HIP_WDF_DP24
+  if (c->NANG == 24 && c->real_bytes == 8) return "24 directions in double precision";
+#endif
+  if (implsch4_choice(c).build != Implsch4Build::rare) return nullptr;
+  if (c->p.lciwa2) return "LCIWA2";
+  if (c->p.lwnemocouwrs) return "LWNEMOCOUWRS";
+  if (c->p.lwnemocoustrn) return "LWNEMOCOUSTRN";
+  if (c->p.isnonlin > 1) return "ISNONLIN 2";
+  if (c->p.icode != 3) return "ICODE 1/2";
+  if (!c->p.lwvflx_snl) return "LWVFLX_SNL = F";
+  return "IPHYS 0 or ISNONLIN 1 beside each other or beside LLGCBZ0 / LLNORMAGAM";
+}
+int ecwam_hip_wdfluxes_supported(ecwam_hip_ctx* c) {
+  if (!c) { fail("null context"); return 0; }
+  if (!c->implsch_why.empty()) { fail("ecwam_hip_wdfluxes: " + c->implsch_why); return 0; }
+  if (const char* w = wdfluxes_uncovered(c)) { fail(std::string("ecwam_hip_wdfluxes: not covered: ") + w); return 0; }
+  return 1;
+}
+int ecwam_hip_wdfluxes(ecwam_hip_ctx* c, int kijs, int kijl, const void* fl1, const void* wvprpt, const void* ff, void* intf, int* mij, void* xllws,
+                       double* wam2nemo, void* stream) {
+  if (!c) return fail("null context");
+  if (kijl < kijs || kijs < 0) return fail("ecwam_hip_wdfluxes: bad range");
+  HIPCHK(hipSetDevice(c->device));
+  if (kijl > kijs && (!fl1 || !wvprpt || !ff || !intf || !mij || !xllws)) return fail("ecwam_hip_wdfluxes: null pointer");
+  if (kijl > kijs && c->p.lwnemocou && !wam2nemo) return fail("ecwam_hip_wdfluxes: LWNEMOCOU needs the WAVE2OCEAN buffer");
+  if (!c->p.lwnemocou) wam2nemo = nullptr;
+  hipStream_t s = (hipStream_t)stream;
+  if (!c->implsch_why.empty()) return fail("ecwam_hip_wdfluxes: " + c->implsch_why);
+  if (const char* w = wdfluxes_uncovered(c)) return fail(std::string("ecwam_hip_wdfluxes: not covered: ") + w);
+  const Implsch4Choice b = implsch4_choice(c);
+  if (int rc2 = implsch_reserve_on(c, kijl, s)) return rc2;   // no-op once the buffer covers kijl
+  const int sel = b.build == Implsch4Build::alternate ? (b.alt == 1 ? 2 : 3) : b.ext;
+  const int rc = in_precision(c, [&](auto t) {
+    return launch_wdfluxes<decltype(t)>(c->dtab, kijs, kijl, fl1, wvprpt, ff, intf, mij, xllws, c->fin, wam2nemo, c->NANG, c->NFRE, c->v4_r1, c->v4_r2, c->v4_nh, sel, s);
+  });
+  if (rc == 0) { HIPCHK(hipGetLastError()); return 0; }
+  return fail("ecwam_hip_wdfluxes: no build of k_implsch4 covers the configuration (ecwam_hip_create should have refused it)");
+}
+int ecwam_hip_setice(ecwam_hip_ctx* c, int kijs, int kijl, void* fl1, const void* ff, void* stream) {
+  if (!c) return fail("null context");
+  if (kijl < kijs || kijs < 0) return fail("ecwam_hip_setice: bad range");
+  HIPCHK(hipSetDevice(c->device));
+  if (kijl > kijs && (!fl1 || !ff)) return fail("ecwam_hip_setice: null pointer");
+  if (((uintptr_t)fl1 % 16) != 0) return fail("ecwam_hip_setice: the spectra must be 16-byte aligned");
+  const int rc = in_precision(c, [&](auto t) { return launch_setice<decltype(t)>(c->dtab, kijs, kijl, fl1, ff, c->NANG, c->NFRE, (hipStream_t)stream); });
+  if (rc == 0) { HIPCHK(hipGetLastError()); return 0; }
+  return fail("ecwam_hip_setice: the frequencies of a direction are no whole number of 16-byte chunks");
 }
 
 // bit 0: the one-kernel step covers the context; bit 1: also with fast-wave sub-steps (gin); bit 2: also with the obstructions of

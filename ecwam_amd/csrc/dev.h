@@ -87,6 +87,8 @@ struct DevTab {
   // gravity-capillary tables, 1-based like the reference
   T XK_GC[MAXGC], XKM_GC[MAXGC], OMEGA_GC[MAXGC], OMXKM3_GC[MAXGC], CM_GC[MAXGC], C2OSQRTVG_GC[MAXGC];
   T XKMSQRTVGOC2_GC[MAXGC], OM3GMKM_GC[MAXGC], DELKCC_GC_NS[MAXGC], DELKCC_OMXKM3_GC[MAXGC];
+  // WDFLUXES' own LCFLX = LWFLUX .OR. LWFLUXOUT (wdfluxes.F90:156; IMPLSCH's also ORs LWNEMOCOU).  Last, so that no other member moves.
+  int LCFLX_WD;
 };
 
 // ---- precision-generic math ---------------------------------------------------------------------

@@ -221,13 +221,24 @@ __device__ __forceinline__ T v4_allmax1(T v, const V4Rot<T>& r) {
   }
 }
 
+// UNI (the WDFLUXES builds): the value of the point's lane j = 0 on every lane of the point.  With 48 / 24 / 12 directions the all-reduce leaves
+// totals that differ in the last bit between the lanes of a point, and every lane stores its own to the row table: which one stays depends on
+// the spare lanes that shadow the point, i.e. on the point's place in the wave -- a call over a range of rows would not equal two calls over its
+// halves bit for bit.  (36 directions: the same bits on every lane as it is.)
+template <int G, bool UNI, typename T>
+__device__ __forceinline__ T v4_uni(T v, int p) {
+  if constexpr (UNI && G != 18) return v4_bp(4 * (p * G), v);
+  else return v;
+}
+
 // The positive wind input of a row summed over the directions of the point -> the point's row table in LDS (SINPUT's second call;
 // weighted below the cut-off once MIJ is known, stresso.F90:160-168).  36 directions: the extras are folded into lanes 0, 1 of the point's
 // DPP row, four row rotations, every lane of the row holds the total and stores it (the same value at the same address); the extras'
 // own row of 16 lanes sums a mixture nobody reads: their store goes to a private slot (spw).  No trip through global memory (rounds 1
 // and 2 parked the per-lane shares in the point's FL1 block: 1.1 GB written and read back per O320 launch).
-template <int G, typename T>
-__device__ __forceinline__ void v4_row_total_to_lds(T v, const V4Rot<T>& r, T* spw, int m) {
+// UNI (the WDFLUXES builds, 48 / 24 / 12 directions): the total of the point's lane j = 0 on every lane before the store (v4_uni below).
+template <int G, typename T, bool UNI = false>
+__device__ __forceinline__ void v4_row_total_to_lds(T v, const V4Rot<T>& r, T* spw, int m, int p = 0) {
   if constexpr (G == 18) {
     v = v + r.fold * v4_bp(r.a0, v);
     v = v + v4_dpp<V4_ROW_ROR(8)>(v);
@@ -237,7 +248,7 @@ __device__ __forceinline__ void v4_row_total_to_lds(T v, const V4Rot<T>& r, T* s
   } else {
     v = v4_allsum1<G, T>(v, r);
   }
-  spw[m] = v;
+  spw[m] = v4_uni<G, UNI>(v, p);
 }
 
 // the pair (X(2j+r), X(2j+r+1)) of an LDS row; sh[i] = index of element (2j + 2(i-NSH)) mod NANG of the lane's point in a row
@@ -734,7 +745,7 @@ __device__ void taut_z0_b_rows(const DevTab<T>& tb, int l16, int IUSFG, T HALP, 
 // integrals X, Y of the frequencies the lane owns (m = s G + j), the FEMEANWS integrands (wse: x = SUM DFIM F, y = SUM DFIMOFR F
 // over the windsea bins; wslast = windsea part of the last row), apl (negative wind input per direction) and -- LLSNEG -- the
 // wind-input coefficient of every row into gfl (the point's XLLWS block, [M][K]).
-template <typename T, int NANG, int PP, int NGST, bool LLSNEG>
+template <typename T, int NANG, int PP, int NGST, bool LLSNEG, bool UNI = false>
 __device__ void v4_sinput(const DevTab<T>& tb, const V4Ctx<T, NANG, PP>& L, T UFRIC, T Z0M, T RAORW, T SIG_N, T TEMP2, T PTURB, T AIRD_PVISC,
                           T sinwd, T coswd, T* __restrict__ gfl, T* __restrict__ gsp, unsigned long long& xm0, unsigned long long& xm1, V2<T>& wse,
                           V2<T>& wslast, V2<T>& apl, T (&rX)[V4_NS(NANG)], T (&rY)[V4_NS(NANG)], T* __restrict__ sXY) {
@@ -867,7 +878,7 @@ __device__ void v4_sinput(const DevTab<T>& tb, const V4Ctx<T, NANG, PP>& L, T UF
         yrow += red[2 * ig + 1];
       }
       xrow = AVG * xrow; yrow = AVG * yrow;
-      if constexpr (LLSNEG) gsp[m] = red[2 * NGST];      // (v4_row_total_to_lds: every lane of the row stores the same total)
+      if constexpr (LLSNEG) gsp[m] = v4_uni<G, UNI>(red[2 * NGST], L.p);      // (v4_row_total_to_lds: every lane of the row stores the same total)
     } else
     if (sizeof(T) == 4 || __builtin_amdgcn_ballot_w64(xl0 || xl1) != 0ull) {
       {
@@ -901,7 +912,7 @@ __device__ void v4_sinput(const DevTab<T>& tb, const V4Ctx<T, NANG, PP>& L, T UF
       apl = apl + (fl * f - sp) * row[4];
       *reinterpret_cast<V2<T>*>(gfl + (size_t)m * NANG) = fl;
       // the row's positive input summed over the directions -> the point's row table (weighted below the cut-off once MIJ is known)
-      if constexpr (!REDN) v4_row_total_to_lds<G, T>(sp.x + sp.y, L.rot, gsp, m);
+      if constexpr (!REDN) v4_row_total_to_lds<G, T, UNI>(sp.x + sp.y, L.rot, gsp, m, L.p);
     }
     if (xl0) xm0 |= (1ull << m);
     if (xl1) xm1 |= (1ull << m);
@@ -916,7 +927,7 @@ __device__ void v4_sinput(const DevTab<T>& tb, const V4Ctx<T, NANG, PP>& L, T UF
 // SINPUT_ARD with the normalised growth rate (LLNORMAGAM = T, sinput_ard.F90:380-437; TAUWSHELTER = 0 in that physics: no sheltering
 // recurrence, the growth direction is the wind direction).  Per row and gust state one all-reduce for SUMF / SUMFSIN2, one for the row
 // integrals.  xng: plane [M] of CONSTN RNFAC / RAORW XK2CG(M) (filled here, in the plane SQRT(WAVNUM) leaves free between the two FKMEAN).
-template <typename T, int NANG, int PP, int NGST, bool LLSNEG>
+template <typename T, int NANG, int PP, int NGST, bool LLSNEG, bool UNI = false>
 __device__ void v4_sinput_n(const DevTab<T>& tb, const V4Ctx<T, NANG, PP>& L, const T* __restrict__ xk2cg, T UFRIC, T Z0M, T RAORW, T RNFAC,
                             T SIG_N, T TEMP2, T PTURB, T AIRD_PVISC, V2<T> coswdif, V2<T> sinwdif2, T* __restrict__ gfl, T* __restrict__ gsp,
                             unsigned long long& xm0, unsigned long long& xm1, V2<T>& wse, V2<T>& wslast, V2<T>& apl,
@@ -1032,7 +1043,7 @@ __device__ void v4_sinput_n(const DevTab<T>& tb, const V4Ctx<T, NANG, PP>& L, co
     if (LLSNEG) {
       apl = apl + (fl * f - sp) * row[4];
       *reinterpret_cast<V2<T>*>(gfl + (size_t)m * NANG) = fl;
-      v4_row_total_to_lds<G, T>(sp.x + sp.y, L.rot, gsp, m);
+      v4_row_total_to_lds<G, T, UNI>(sp.x + sp.y, L.rot, gsp, m, L.p);
     }
     if (xl0) xm0 |= (1ull << m);
     if (xl1) xm1 |= (1ull << m);
@@ -1049,7 +1060,7 @@ __device__ void v4_sinput_n(const DevTab<T>& tb, const V4Ctx<T, NANG, PP>& L, co
 // waits for them).  Same outputs as v4_sinput.  coswdif: COS(TH - WDWAVE) of the lane's pair.  NRM (the builds that carry LLNORMAGAM,
 // decided at run time by norma): the growth rate of a row and gust state renormalised by GAMNORMA = (1 + ZNZ SUMFSIN2) / (1 + ZNZ SUMF)
 // (sinput_jan.F90:329-357; one all-reduce per row and gust state); xng: plane [M] of CONSTN RNFAC / RAORW XK2CG(M), filled here.
-template <typename T, int NANG, int PP, int NGST, bool LLSNEG, bool NRM = false>
+template <typename T, int NANG, int PP, int NGST, bool LLSNEG, bool NRM = false, bool UNI = false>
 __device__ void v4_sinput_jan(const DevTab<T>& tb, const V4Ctx<T, NANG, PP>& L, T UFRIC, T Z0M, T RAORW, T SIG_N, V2<T> coswdif,
                               T* __restrict__ gfl, T* __restrict__ gsp, unsigned long long& xm0, unsigned long long& xm1, V2<T>& wse,
                               V2<T>& wslast, V2<T>& apl, T (&rX)[V4_NS(NANG)], T (&rY)[V4_NS(NANG)], T* __restrict__ sXY,
@@ -1158,7 +1169,7 @@ __device__ void v4_sinput_jan(const DevTab<T>& tb, const V4Ctx<T, NANG, PP>& L, 
     if (LLSNEG) {
       apl = apl + (fl * f - sp) * row[4];
       *reinterpret_cast<V2<T>*>(gfl + (size_t)m * NANG) = fl;
-      v4_row_total_to_lds<G, T>(sp.x + sp.y, L.rot, gsp, m);
+      v4_row_total_to_lds<G, T, UNI>(sp.x + sp.y, L.rot, gsp, m, L.p);
     }
     if (xl0) xm0 |= (1ull << m);
     if (xl1) xm1 |= (1ull << m);
@@ -1215,6 +1226,10 @@ __device__ __forceinline__ T v4_sdice3_alp(const DevTab<T>& tb, int m, T CITHICK
 // them, writes XLLWS, parks the wind-input coefficient in the rows of wi[ij][M][K] (context-owned) and hands its scalars over in fin;
 // PART 2 loads the spectrum again, re-applies SDEPTHLIM's scale and tail (the same operations: the same bits) and runs the sweep, the
 // fluxes, the tail and the stores.  Same source, same results bit for bit; two smaller functions for the compiler.
+// PART 3 = WDFLUXES (wdfluxes.F90:156-306; the source terms evaluated once for the fluxes, nothing advanced: OUTSTEP0 before the first step and
+// after a restart): FKMEAN of FL1 as it stands, ONE SINFLX call in the form of the second one (NGST = 2, LLSNEG, PHIWA) on UFRIC / Z0M as FF holds
+// them, and -- with WDFLUXES' own LCFLX (DevTab::LCFLX_WD) -- the SDISSIP + SNONLIN sweep for SSOURCE only, WNFLUXES' sums, FEMEANWS and
+// STOKESDRIFT of FL1.  No SDEPTHLIM, no noise floor, no TAUT_Z0, no SDIWBK / SBOTTOM / sea-ice rates, no update; FL1 and FF are only read.
 // ADV: 0 = the tile is loaded from FL1 (IMPLSCH on its own, behind a PROPAGS2 kernel); 1 = the tile load IS the advection (round 6:
 // v4_advect_tile above -- PROPAGS2 of the wave's points from the rows of adv.f_in straight into the tile, the new spectrum stored to the rows
 // of fl1, which must be another buffer: one kernel per WAMINTGR step); 3 = the same for the native O1280 mode: the fast waves with their own
@@ -1247,6 +1262,8 @@ k_implsch4(const DevTab<T>* __restrict__ tp, int kijs, int kijl, T* __restrict__
   typedef T VT __attribute__((ext_vector_type(VEC)));
   extern __shared__ __align__(16) unsigned char smem_raw[];
   const DevTab<T>& tb = *tp;
+  constexpr bool WDF = (PART == 3);
+  static_assert(!WDF || (!RARE && ADV == 0), "WDFLUXES: the common and the alternate builds, the tile loaded from FL1");
   T* sT = reinterpret_cast<T*>(smem_raw);          // [NFRE + V4_NSTG][PP][NANG]
   T* sStg = sT + NFRE * RS;                        // staging rows 0..3
   T* sFac4 = sT + (NFRE + V4_NSTG) * RS;           // [PP][NFRE][4]
@@ -1511,7 +1528,7 @@ k_implsch4(const DevTab<T>* __restrict__ tp, int kijs, int kijl, T* __restrict__
     }
   } else {
     T sc = T(1);
-    if (tb.LBIWBK) {
+    if (!WDF && tb.LBIWBK) {      // (WDFLUXES: no SDEPTHLIM)
       V2<T> s = z2;
       for (int m = 0; m < NFRE; m++) {
         const V2<T> f = *reinterpret_cast<const V2<T>*>(tF + m * RS);
@@ -1529,7 +1546,7 @@ k_implsch4(const DevTab<T>* __restrict__ tp, int kijs, int kijl, T* __restrict__
     V2<T> s0 = z2, s1 = z2, s2 = z2, so = z2;
     // branch-free rows: without LBIWBK the scale is 1 and the floor -infinity (both exact), the row is stored back unchanged; the
     // last row (raised to the noise floor for the orbital integrals only) is peeled off
-    const T flo = tb.LBIWBK ? tb.EPSMIN : -std::numeric_limits<T>::infinity();
+    const T flo = (!WDF && tb.LBIWBK) ? tb.EPSMIN : -std::numeric_limits<T>::infinity();
     auto row202 = [&](int m, bool last) {
       V2<T> f = *reinterpret_cast<const V2<T>*>(tF + m * RS) * sc;
       f.x = m_max(f.x, flo); f.y = m_max(f.y, flo);
@@ -1541,7 +1558,7 @@ k_implsch4(const DevTab<T>* __restrict__ tp, int kijs, int kijl, T* __restrict__
       s2.x = s2.x + (sqm * dfm) * t;
       if (last) {
         s2.y = t;
-        f.x = m_max(f.x, FLM.x); f.y = m_max(f.y, FLM.y);   // the orbital integrals see the raised tail
+        if constexpr (!WDF) { f.x = m_max(f.x, FLM.x); f.y = m_max(f.y, FLM.y); }   // the orbital integrals see the raised tail (WDFLUXES: FLM = 0)
       }
       const T to = f.x + f.y;
       so = so + V2<T>{dfm * (sig * sig), dfm} * to;
@@ -1594,7 +1611,7 @@ k_implsch4(const DevTab<T>* __restrict__ tp, int kijs, int kijl, T* __restrict__
       WSYNC();
     }
   };
-  if (PART != 2 && gcb) {
+  if (PART != 2 && !WDF && gcb) {      // (WDFLUXES: LUPDTUS = F, neither HALPHAP nor AIRSEA)
     // HALPHAP (halphap.F90:68-112, meansqs_lf.F90:80-100, femean.F90:84-121): Phillips parameter of the wind-sea half plane
     const V2<T> wd = {__builtin_signbit(coswdif.x) ? T(0) : T(1), __builtin_signbit(coswdif.y) ? T(0) : T(1)};
     V2<T> sa = z2, sb = z2;   // (XMSS, EM), (FM, last row of MAX(F WD, EPSMIN))
@@ -1698,8 +1715,19 @@ k_implsch4(const DevTab<T>* __restrict__ tp, int kijs, int kijl, T* __restrict__
   T FMEANWS, EMW;
   int MIJ;
   T SDS;
-  T* gx = (PART == 0 ? xllws : wi) + (size_t)ij * N + 2 * j;   // this lane's pair in row 0 of the block that holds the wind-input coefficient
+  T* gx = ((PART == 0 || WDF) ? xllws : wi) + (size_t)ij * N + 2 * j;   // this lane's pair in row 0 of the block that holds the wind-input coefficient
   if constexpr (PART != 2) {
+  if constexpr (WDF) {
+    // WDFLUXES' one SINFLX call has the form of the second one; of the scalar stage only what SINPUT itself does with NGST = 2 and LLSNEG:
+    // WSIGSTAR and the swell set-up, on UFRIC / Z0M as they came
+    if (lane < PP) {
+      T* q = sSC + lane * NSC;
+      q[C_SIGN] = wsigstar(tb, q[C_WSWAVE], q[C_UFRIC], q[C_Z0M], q[C_WSTAR]);
+      swell_setup_pt(tb, q);
+    }
+    WSYNC();
+    SDS = T(0);
+  } else {
   if constexpr (JAN) v4_sinput_jan<T, NANG, PP, 1, false, EXT>(tb, L, UFRIC, Z0M, RAORW, T(0), coswdif, nullptr, nullptr, xm0, xm1, wse, wslast, apl, rX, rY, sXY,
                                                                  norma, sinwdif2, wp + 3 * NFRE, RNFAC);
   else if (norma) v4_sinput_n<T, NANG, PP, 1, false>(tb, L, wp + 3 * NFRE, UFRIC, Z0M, RAORW, RNFAC, T(0), T(0), T(0), T(0), coswdif, sinwdif2, nullptr, nullptr,
@@ -1738,14 +1766,15 @@ k_implsch4(const DevTab<T>* __restrict__ tp, int kijs, int kijl, T* __restrict__
   WSYNC();
   UFRIC = c[C_UFRIC]; Z0M = c[C_Z0M];
   SDS = c[C_SDS];
+  }
   V4_PHASE_EXIT(204);
   // ---- second SINFLX call: wind-input coefficient (parked in the point's XLLWS block, [M][K]; PART 1: in the rows of wi), XLLWS, MIJ,
   //      wave stress, PHIWA
-  if constexpr (JAN) v4_sinput_jan<T, NANG, PP, 2, true, EXT>(tb, L, UFRIC, Z0M, RAORW, c[C_SIGN], coswdif, gx, gsp, xm0, xm1, wse, wslast, apl, rX, rY, sXY,
+  if constexpr (JAN) v4_sinput_jan<T, NANG, PP, 2, true, EXT, WDF>(tb, L, UFRIC, Z0M, RAORW, c[C_SIGN], coswdif, gx, gsp, xm0, xm1, wse, wslast, apl, rX, rY, sXY,
                                                                 norma, sinwdif2, wp + 3 * NFRE, RNFAC);
-  else if (norma) v4_sinput_n<T, NANG, PP, 2, true>(tb, L, wp + 3 * NFRE, UFRIC, Z0M, RAORW, RNFAC, c[C_SIGN], c[C_TEMP2], c[C_PTURB], c[C_AIRDPVISC], coswdif,
+  else if (norma) v4_sinput_n<T, NANG, PP, 2, true, WDF>(tb, L, wp + 3 * NFRE, UFRIC, Z0M, RAORW, RNFAC, c[C_SIGN], c[C_TEMP2], c[C_PTURB], c[C_AIRDPVISC], coswdif,
                                                    sinwdif2, gx, gsp, xm0, xm1, wse, wslast, apl, rX, rY, sXY);
-  else v4_sinput<T, NANG, PP, 2, true>(tb, L, UFRIC, Z0M, RAORW, c[C_SIGN], c[C_TEMP2], c[C_PTURB], c[C_AIRDPVISC], sinwd, coswd, gx, gsp, xm0, xm1, wse,
+  else v4_sinput<T, NANG, PP, 2, true, WDF>(tb, L, UFRIC, Z0M, RAORW, c[C_SIGN], c[C_TEMP2], c[C_PTURB], c[C_AIRDPVISC], sinwd, coswd, gx, gsp, xm0, xm1, wse,
                                        wslast, apl, rX, rY, sXY);
   femws_finish(wse, wslast, FMEANWS, EMW);
   MIJ = frcutindex4(FMEANWS, UFRIC);
@@ -1811,7 +1840,7 @@ k_implsch4(const DevTab<T>* __restrict__ tp, int kijs, int kijl, T* __restrict__
   //   from global memory as vector loads one interaction (eight rows) ahead.
   V2<T> a_t = z2, a_x = z2;
   V2<T> a_ice = z2;      // RARE: integrand of the ice radiative stress
-  {
+  if (!WDF || tb.LCFLX_WD) {      // (WDFLUXES without its LCFLX ends with SINFLX: wdfluxes.F90:217)
     T ENHFR = m_max(T(0.75) * DEPTH * AKMEAN, T(0.5));
     ENHFR = T(1) + (T(5.5) / ENHFR) * (T(1) - T(0.833) * ENHFR) * m_exp(-T(1.25) * ENHFR);
     // ISNONLIN = 1 (snonlin.F90:138-150): ENH(MC) = MAX(MIN(ENH_MAX, TRANSF(k(MC), DEPTH)), ENH_MIN) per interaction frequency; lane j of
@@ -1950,7 +1979,7 @@ k_implsch4(const DevTab<T>* __restrict__ tp, int kijs, int kijl, T* __restrict__
     const T DELT = (T)tb.IDELT, DELTM = T(1) / DELT, DELT5 = tb.XIMP * DELT;
     const bool shallow_brk = tb.LBIWBK && (DEPTH < T(50));
     const T USFM = UFRIC * m_max(FMEANWS, FMEAN);
-    const T FSNL = (tb.LCFLX && tb.LWVFLX_SNL) ? T(1) : T(0);
+    const T FSNL = ((WDF ? tb.LCFLX_WD : tb.LCFLX) && tb.LWVFLX_SNL) ? T(1) : T(0);
     const T SDSL = shallow_brk ? SDS : T(0);
     const T BETA = (tb.LICERUN && tb.LCISCAL) ? T(1) - CICOVER : T(1);
     const int NRED = tb.NFRE_RED, MLST = tb.MLSTHG;
@@ -2009,6 +2038,7 @@ k_implsch4(const DevTab<T>* __restrict__ tp, int kijs, int kijl, T* __restrict__
       if constexpr (RARE) {
         if (tb.LCFLX && !tb.LWVFLX_SNL) ss = fldw * f;      // SL after SDISSIP, before SNONLIN, unmodulated (implsch.F90:280-288)
       }
+      if constexpr (!WDF) {      // (WDFLUXES takes SSOURCE and stops: what follows it there feeds no output, and nothing is advanced)
       {
         const T sd = (m < NRED) ? SDSL : T(0);                        // SDIWBK where the point is shallow (SDSL = 0 elsewhere: exact)
         sl = sl - sd * f; fld = fld - sd;
@@ -2048,6 +2078,7 @@ k_implsch4(const DevTab<T>* __restrict__ tp, int kijs, int kijl, T* __restrict__
         fn = fc;
       }
       *reinterpret_cast<V2<T>*>(tFw + m * RS) = fn;
+      }
       const T rh = rhowg * m_min(m_max(MIJh - (T)(m + 1), T(0)), T(1));
       a_t = a_t + rh * ss;
       a_x = a_x + (u_cinv * rh) * ss;
@@ -2079,7 +2110,8 @@ k_implsch4(const DevTab<T>* __restrict__ tp, int kijs, int kijl, T* __restrict__
       const int mq = __builtin_amdgcn_readlane(MIJ, G == 18 ? 16 * q : q * G);
       mijmax = mq > mijmax ? mq : mijmax;
     }
-    const bool whole = tb.LWFLUX != 0 || wrs;      // (the ice radiative stress integrates SLICE over every row, wnfluxes.F90:178-196)
+    // (the ice radiative stress integrates SLICE over every row, wnfluxes.F90:178-196; WDFLUXES: FEMEANWS is of FL1 itself, never whole)
+    const bool whole = !WDF && (tb.LWFLUX != 0 || wrs);
     const int UPD_LIM = whole ? NFRE : mijmax;                                      // rows m < UPD_LIM (0-based) are updated
     const int DIA_LIM = whole ? MLST : (mijmax + 4 < MLST ? mijmax + 4 : MLST);     // interactions MC <= DIA_LIM contribute to them
     const int MC_END = whole ? MLST : (mijmax + 5 < MLST ? mijmax + 5 : MLST);      // row MIJ is updated at the top of interaction MIJ + 5
@@ -2298,7 +2330,7 @@ k_implsch4(const DevTab<T>* __restrict__ tp, int kijs, int kijl, T* __restrict__
 
   // ---- WNFLUXES (wnfluxes.F90:147-190): the directional sums of the flux accumulators; the rest of it in k_implsch4_fin
   T PHILF = T(0), XSTRESS = T(0), YSTRESS = T(0);
-  if (tb.LCFLX) {
+  if (WDF ? tb.LCFLX_WD : tb.LCFLX) {
     const V2<T> sx = a_x * L.sinth, sy = a_x * L.costh;
     const V2<T> r0 = v4_allsum<G, T>(V2<T>{a_t.x + a_t.y, sx.x + sx.y}, L.rot);
     YSTRESS = v4_allsum1<G, T>(sy.x + sy.y, L.rot);
@@ -2326,7 +2358,7 @@ k_implsch4(const DevTab<T>* __restrict__ tp, int kijs, int kijl, T* __restrict__
   }
   WSYNC();
   T EMEANWS = T(0);
-  if (tb.LWFLUX) {  // femeanws.F90:84-123 on the new spectrum, before the tail is replaced
+  if (tb.LWFLUX) {  // femeanws.F90:84-123 on the new spectrum, before the tail is replaced (WDFLUXES: on FL1)
     V2<T> we = z2, wl = z2;   // windsea (EM, FM), windsea part of the last row
     for (int m = 0; m < NFRE; m++) {
       const V2<T> f = *reinterpret_cast<const V2<T>*>(tF + m * RS);
@@ -2338,7 +2370,7 @@ k_implsch4(const DevTab<T>* __restrict__ tp, int kijs, int kijl, T* __restrict__
     femws_finish(we, wl, FMEANWS, EMEANWS);
   }
   V4_PHASE_EXIT(208);
-  {  // imphftail.F90: TEMP2(M) / TEMP1 = (XK2CG WAVNUM)(MIJ) / (XK2CG WAVNUM)(M)
+  if constexpr (!WDF) {  // imphftail.F90: TEMP2(M) / TEMP1 = (XK2CG WAVNUM)(MIJ) / (XK2CG WAVNUM)(M)
     V4_CHK(MIJ >= 1 && MIJ <= NFRE);
     const T B1 = L.fac4[(MIJ - 1) * 4 + Q4_BSC];
     const V2<T> tf = *reinterpret_cast<const V2<T>*>(tF + (MIJ - 1) * RS);
@@ -2347,7 +2379,7 @@ k_implsch4(const DevTab<T>* __restrict__ tp, int kijs, int kijl, T* __restrict__
       *reinterpret_cast<V2<T>*>(tFw + m * RS) = V2<T>{m_max(tm * tf.x, FLM.x), m_max(tm * tf.y, FLM.y)};
     }
   }
-  if (tb.LICERUN && tb.LMASKICE) {  // setice.F90:67-86
+  if (!WDF && tb.LICERUN && tb.LMASKICE) {  // setice.F90:67-86 (OUTSTEP0 calls it on its own: k_setice)
     T CIREDUC, ICEFREE;
     if (CICOVER > tb.CITHRSH) { CIREDUC = m_max(tb.EPSMIN, T(1) - CICOVER); ICEFREE = T(0); }
     else { CIREDUC = T(0); ICEFREE = T(1); }
@@ -2398,7 +2430,7 @@ k_implsch4(const DevTab<T>* __restrict__ tp, int kijs, int kijl, T* __restrict__
   WSYNC();
   V4_PHASE_EXIT(209);
   // ---- store FL1 (16-byte chunks gathered from VEC rows of the tile), XLLWS(K,M) from the bit masks, per-point scalars
-  {
+  if constexpr (!WDF) {
     constexpr int NV = N / VEC, NIT = (NV + 63) / 64;
     int k = lane / NC, r = lane - k * NC;
 #pragma unroll
@@ -2423,16 +2455,18 @@ k_implsch4(const DevTab<T>* __restrict__ tp, int kijs, int kijl, T* __restrict__
     }
   }
   V4_PHASE_EXIT(210);
-  if constexpr (PART == 0) store_xllws();   // every wind-input row parked in this block has been read by now
+  if constexpr (PART == 0 || WDF) store_xllws();   // every wind-input row parked in this block has been read by now
   V4_PHASE_EXIT(211);
   if (j == 0) {
-    T* fo = ffa + (size_t)ij * ECWAM_HIP_NFF;
-    fo[7] = UFRIC; fo[10] = Z0M; fo[11] = Z0B; fo[12] = CHRNCK;   // TAUW, TAUWDIR: k_implsch4_fin
-    if (RARE && tb.ICODE != 3) fo[3] = WSWAVE;                    // friction-velocity forcing: the 10 m wind is an output (airsea.F90:107-115)
+    if constexpr (!WDF) {      // (WDFLUXES: the forcing is only read)
+      T* fo = ffa + (size_t)ij * ECWAM_HIP_NFF;
+      fo[7] = UFRIC; fo[10] = Z0M; fo[11] = Z0B; fo[12] = CHRNCK;   // TAUW, TAUWDIR: k_implsch4_fin
+      if (RARE && tb.ICODE != 3) fo[3] = WSWAVE;                    // friction-velocity forcing: the 10 m wind is an output (airsea.F90:107-115)
+    }
     T* io = intfa + (size_t)ij * ECWAM_HIP_NINTF;
-    io[2] = USTOKES; io[3] = VSTOKES;
+    if (!WDF || tb.LCFLX_WD) { io[2] = USTOKES; io[3] = VSTOKES; }      // (WDFLUXES: STOKESTRN inside its LCFLX, wdfluxes.F90:303)
     T* fr = fin + (size_t)ij * V4_NFIN;
-    if constexpr (PART == 0) {   // (PART 2: the first kernel wrote these)
+    if constexpr (PART == 0 || WDF) {   // (PART 2: the first kernel wrote these)
       fr[FIN_AIRD] = AIRD; fr[FIN_UFRIC] = UFRIC; fr[FIN_Z0M] = Z0M; fr[FIN_MIJ] = c[C_MIJ];
       fr[FIN_XS] = c[C_XS]; fr[FIN_YS] = c[C_YS]; fr[FIN_F1DCOS3] = c[C_F1DCOS3]; fr[FIN_F1DCOS2] = c[C_F1DCOS2];
       fr[FIN_F1DSIN2] = c[C_F1DSIN2]; fr[FIN_F1D] = c[C_F1D]; fr[FIN_RNFAC] = c[C_RNFAC]; fr[FIN_PHIWA] = c[C_PHIWA];
@@ -2452,7 +2486,8 @@ k_implsch4(const DevTab<T>* __restrict__ tp, int kijs, int kijl, T* __restrict__
 
 // The scalar start of the time step, one sea point per lane (sinflx.F90:105-122): direction of the wind, RNFAC, the first TAUT_Z0
 // (taut_z0.F90:288-340; with LLGCBZ0 only its COSDIFF -- the gravity-capillary iteration needs the spectrum and stays in k_implsch4).
-template <typename T, bool EXT, bool RARE = false>
+// WDF (WDFLUXES, LUPDTUS = F): no TAUT_Z0 -- UFRIC, Z0M, Z0B and CHRNCK go through as FF holds them.
+template <typename T, bool EXT, bool RARE = false, bool WDF = false>
 __global__ void __launch_bounds__(64) k_implsch4_pre(const DevTab<T>* __restrict__ tp, int kijs, int kijl, const T* __restrict__ ffa,
                                                      T* __restrict__ fin) {
   const DevTab<T>& tb = *tp;
@@ -2466,8 +2501,9 @@ __global__ void __launch_bounds__(64) k_implsch4_pre(const DevTab<T>* __restrict
   if (EXT && tb.LLNORMAGAM && tb.LLCAPCHNK) RNFAC = T(1) + tb.DTHRN_A * (T(1) + m_tanh(WSWAVE - tb.DTHRN_U));
   fr[FIN_RNFAC] = RNFAC;
   T UFRIC = ff[7], Z0M = ff[10], Z0B = ff[11], CHRNCK = ff[12];
-  if (EXT && tb.LLGCBZ0) fr[FIN_COSDIFF] = m_cos(WDWAVE - ff[9]);
-  if (RARE && tb.ICODE != 3) {
+  if (!WDF && EXT && tb.LLGCBZ0) fr[FIN_COSDIFF] = m_cos(WDWAVE - ff[9]);
+  if (WDF) {      // (nothing more: the scalars below go through as they came)
+  } else if (RARE && tb.ICODE != 3) {
     // friction-velocity forcing (airsea.F90:100-117): Z0WAVE (z0wave.F90:73-92), then the 10 m wind from the log profile
     const T ALPHAOG = (tb.LLCAPCHNK ? chnkmin(tb, WSWAVE) : tb.ALPHA) * tb.GM1;
     const T UST2 = UFRIC * UFRIC, UST3 = UST2 * UFRIC;
@@ -2483,7 +2519,9 @@ __global__ void __launch_bounds__(64) k_implsch4_pre(const DevTab<T>* __restrict
 // The scalar end of the time step, one sea point per lane: STRESSO's second call (stresso.F90:180-229 with tau_phi_hf.F90:125-301:
 // TAUW, TAUWDIR, PHIWA) and WNFLUXES' point-wise part (wnfluxes.F90:190-330, LWNEMOCOU = F) from the row of scalars k_implsch4 left
 // in fin(:, IJ).  On k_implsch4's waves these two dependent chains kept PP lanes busy; here every lane has a point.
-template <typename T, bool EXT>
+// WDF (WDFLUXES): STRESSO's TAUW / TAUWDIR are locals there (FF is not written), LCFLX is WDFLUXES' own, and WNFLUXES runs with LNUPD = F: of
+// WAVE2OCEAN only STOKESTRN's columns 0, 1 are set, inside that LCFLX.
+template <typename T, bool EXT, bool WDF = false>
 __global__ void __launch_bounds__(64) k_implsch4_fin(const DevTab<T>* __restrict__ tp, int kijs, int kijl, const T* __restrict__ fin,
                                                      T* __restrict__ ffa, T* __restrict__ intfa, double* __restrict__ w2n) {
   const DevTab<T>& tb = *tp;
@@ -2502,8 +2540,9 @@ __global__ void __launch_bounds__(64) k_implsch4_fin(const DevTab<T>* __restrict
   stresso_point<T, EXT>(tb, c, true);
   const T PHIWA = c[C_PHIWA];
   T* fo = ffa + (size_t)ij * ECWAM_HIP_NFF;
-  fo[8] = c[C_TAUW]; fo[9] = c[C_TAUWDIR];
-  if (tb.LCFLX) {
+  if constexpr (!WDF) { fo[8] = c[C_TAUW]; fo[9] = c[C_TAUWDIR]; }
+  const bool lcflx = WDF ? tb.LCFLX_WD != 0 : tb.LCFLX != 0;
+  if (lcflx) {
     const T EPSUS3 = tb.EPSUS * m_sqrt(tb.EPSUS);
     // with an explicit ice attenuation term the blending with the ice-covered fluxes starts at CICOVER = 0 (wnfluxes.F90:206-214)
     const bool sdice_on = tb.LCIWA1 || tb.LCIWA2 || tb.LCIWA3;
@@ -2544,7 +2583,7 @@ __global__ void __launch_bounds__(64) k_implsch4_fin(const DevTab<T>* __restrict
     T* io = intfa + (size_t)ij * ECWAM_HIP_NINTF;
     io[5] = TAUXD; io[6] = TAUYD; io[7] = TAUOCXD; io[8] = TAUOCYD; io[9] = TAUOC; io[10] = fr[FIN_TAUICX]; io[11] = fr[FIN_TAUICY];
     io[12] = PHIOCD; io[13] = PHIEPS; io[14] = PHIAW;
-    if (tb.LWNEMOCOU && w2n) {  // wnfluxes.F90:304-328 (LNUPD = T; the ice stress of LWNEMOCOUWRS comes from the RARE build of the main kernel, zero otherwise)
+    if (!WDF && tb.LWNEMOCOU && w2n) {  // wnfluxes.F90:304-328 (LNUPD = T; the ice stress of LWNEMOCOUWRS comes from the RARE build of the main kernel, zero otherwise)
       double* q = w2n + (size_t)ij * 13;
       q[3] = (double)PHIEPS; q[4] = (double)TAUOC;
       q[5] = (EM_OC != T(0)) ? 4.0 * (double)m_sqrt(EM_OC) : 0.0;
@@ -2556,7 +2595,7 @@ __global__ void __launch_bounds__(64) k_implsch4_fin(const DevTab<T>* __restrict
     }
   }
   // stokestrn.F90:75-88 (LWNEMOCOUSTRN = F): the Stokes drift k_implsch4 left in INTFLDS
-  if (tb.LWNEMOCOU && w2n && ((tb.LWNEMOCOUSEND && tb.LWCOU) || !tb.LWCOU)) {
+  if ((!WDF || lcflx) && tb.LWNEMOCOU && w2n && ((tb.LWNEMOCOUSEND && tb.LWCOU) || !tb.LWCOU)) {
     const T* io = intfa + (size_t)ij * ECWAM_HIP_NINTF;
     double* q = w2n + (size_t)ij * 13;
     q[0] = tb.LWNEMOCOUSTK ? (double)io[2] : 0.0;

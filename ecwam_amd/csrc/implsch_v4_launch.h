@@ -1,5 +1,5 @@
-// Launch glue of k_implsch4 (implsch_v4.h), shared by the translation units that instantiate it: implsch4.hip (flag sets A and B) and
-// implsch4x.hip (IPHYS = 0, ISNONLIN = 1).
+// Launch glue of k_implsch4 (implsch_v4.h), shared by the translation units that instantiate it: implsch4.hip (flag sets A and B),
+// implsch4x.hip (IPHYS = 0, ISNONLIN = 1) and implsch4w.hip (WDFLUXES on both).
 #pragma once
 #include "implsch_common.h"
 #include "implsch_point.h"
@@ -42,6 +42,25 @@ static int launch4(const void* tab, int kijs, int kijl, void* fl1, const void* w
   // the scalar end of the step (second STRESSO, WNFLUXES), one point per lane, from the rows the kernel above left in fin
   hipLaunchKernelGGL((k_implsch4_fin<T, EXT>), dim3((n + 63) / 64), dim3(64), 0, s, (const DevTab<T>*)tab, kijs, kijl, (const T*)fin, (T*)ff,
                      (T*)intf, w2n);
+  return 0;
+}
+
+// WDFLUXES (PART = 3 of the kernel with the matching pre / fin): fl1 and ff are only read; of intf the flux members, of w2n columns 0, 1 are
+// written, and those only with WDFLUXES' own LCFLX
+template <typename T, int NANG, int PP, int R1, int R2, int NH, bool EXT, bool JAN = false, bool ENHMC = false>
+static int launch4_wdf(const void* tab, int kijs, int kijl, const void* fl1, const void* wvprpt, const void* ff, void* intf, int* mij, void* xllws, void* fin,
+                       double* w2n, hipStream_t s) {
+  const int n = kijl - kijs;
+  constexpr size_t shmem = v4_lds_bytes<T, NANG, PP>();
+  static_assert(shmem <= 160 * 1024, "LDS");
+  hipLaunchKernelGGL((k_implsch4_pre<T, EXT, false, true>), dim3((n + 63) / 64), dim3(64), 0, s, (const DevTab<T>*)tab, kijs, kijl, (const T*)ff, (T*)fin);
+  auto kfn = k_implsch4<T, NANG, PP, R1, R2, NH, EXT, JAN, ENHMC, false, 3>;
+  if (shmem > 64 * 1024) (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
+  // (the kernel's pointer types are those of the time step; this mode stores through neither fl1 nor ff)
+  hipLaunchKernelGGL(kfn, dim3((n + PP - 1) / PP), dim3(64), shmem, s, (const DevTab<T>*)tab, kijs, kijl, (T*)const_cast<void*>(fl1), (const T*)wvprpt,
+                     (T*)const_cast<void*>(ff), (T*)intf, mij, (T*)xllws, (T*)fin, (T*)nullptr, 0, (T*)nullptr, V4Adv<T>{});
+  hipLaunchKernelGGL((k_implsch4_fin<T, EXT, true>), dim3((n + 63) / 64), dim3(64), 0, s, (const DevTab<T>*)tab, kijs, kijl, (const T*)fin,
+                     (T*)const_cast<void*>(ff), (T*)intf, w2n);
   return 0;
 }
 

@@ -46,7 +46,7 @@ template <typename T> void launch_pack(const void* fl, const int* idx, int n, in
 template <typename T> void launch_proenv_pack(int n, int NFRE, const void* wvprpt, const void* om, const void* depth, const void* u, const void* v, void* buf, hipStream_t s);
 template <typename T> void launch_proenv_unpack(int nrows, int NFRE, const void* buf, const void* land, void* wn, void* cg, void* om, void* dep, void* u, void* v, hipStream_t s);
 
-// ---- implsch4.hip, implsch4x.hip, implsch4r.hip, implsch4a.hip: 0 = launched, -1 = no instantiation covers the configuration ------------
+// ---- implsch4.hip, implsch4x.hip, implsch4r.hip, implsch4a.hip, implsch4w.hip: 0 = launched, -1 = no instantiation covers the configuration ------------
 // sel: EXT (flag set B) for launch_implsch4, the variant (1 = IPHYS 0, 2 = ISNONLIN 1) for launch_implsch4x, JAN (IPHYS 0) for launch_implsch4r
 template <typename T> int launch_implsch4(const void* tab, int kijs, int kijl, void* fl1, const void* wvprpt, void* ff, void* intf, int* mij, void* xllws, void* fin, double* w2n,
         void* gfast, int gk, void* wi, int NANG, int NFRE, int r1, int r2, int nh, int sel, hipStream_t s);
@@ -57,6 +57,10 @@ template <typename T> int launch_implsch4r(const void* tab, int kijs, int kijl, 
 template <typename T> int launch_implsch4_adv(const void* tab, int kijs, int kijl, void* fl_out, const void* wvprpt, void* ff, void* intf, int* mij, void* xllws, void* fin, double* w2n,
         const Implsch4AdvArgs* a, int NANG, int NFRE, int r1, int r2, int nh, int ext, hipStream_t s);
 int implsch4_adv_forms(int NANG, int real_bytes);
+// implsch4w.hip: WDFLUXES (sel: 0 flag set A, 1 flag set B, 2 IPHYS 0, 3 ISNONLIN 1) and SETICE; 0 = launched, -1 = not covered
+template <typename T> int launch_wdfluxes(const void* tab, int kijs, int kijl, const void* fl1, const void* wvprpt, const void* ff, void* intf, int* mij, void* xllws, void* fin,
+        double* w2n, int NANG, int NFRE, int r1, int r2, int nh, int sel, hipStream_t s);
+template <typename T> int launch_setice(const void* tab, int kijs, int kijl, void* fl1, const void* ff, int NANG, int NFRE, hipStream_t s);
 int implsch4_fin_row();
 
 // ---- outbs*.hip: 0 = launched (or nothing to do), 1 = unsupported spectral size -------------------------------------------------------------

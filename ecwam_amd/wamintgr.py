@@ -488,6 +488,23 @@ class Wamintgr:
                 self.ctx.set_fastwave_copy(None)
         self.gfast_valid = on
 
+    # ---- OUTSTEP0 (outstep0.F90:106-221): the output before the first time step and after a restart
+    def wdfluxes(self, wam2nemo=None) -> None:
+        """WDFLUXES (wdfluxes.F90): MIJ, XLLWS, the flux members of INTF and the Stokes drift from FL1 as it stands; FL1 and FF are not written."""
+        self.ctx.wdfluxes(0, self.n, self.fl1, self.wvprpt, self.ff, self.intf, self.mij, self.xllws, wam2nemo=wam2nemo)
+
+    def outstep0(self, requested=None, llsource: bool = True, second_order: bool = False, wam2nemo=None):
+        """WDFLUXES (LLSOURCE = F: MIJ = NFRE, XLLWS = 0), SETICE when LICERUN .AND. LMASKICE .AND. LLSOURCE, then OUTBLOCK of `requested`
+        (what outblock() returns; None without a request).  wam2nemo: the WAVE2OCEAN block WDFLUXES needs with LWNEMOCOU."""
+        if llsource:
+            self.wdfluxes(wam2nemo)
+        else:
+            self.ctx.nosource(0, self.n, None, self.mij, self.xllws)
+        if self.cfg.licerun and self.cfg.lmaskice and llsource:
+            self.ctx.setice(0, self.n, self.fl1, self.ff)
+            self.gfast_valid = False      # FL1 changed: the compact fast-wave rows no longer describe it
+        return None if requested is None else self.outblock(requested, second_order)
+
     # ---- the 1:1 step as one kernel (round 6): PROPAGS2 inside IMPLSCH's tile load (ecwam_hip_propags2_implsch)
     def fused_available(self) -> bool:
         """The one-kernel step covers this model: a build exists (36 x 36, common IMPLSCH builds) and the advection is IREFRA = 0 with

@@ -295,6 +295,32 @@ const void *ecwam_hip_device_tables(ecwam_hip_ctx *ctx);
 int ecwam_hip_implsch_reserve(ecwam_hip_ctx *ctx, int npts);
 
 /*
+ * WDFLUXES (wdfluxes.F90:156-306) for rows [kijs,kijl): what OUTSTEP0 (outstep0.F90:108-169) runs before the first time step and after a
+ * restart, so that the output of step 0 has MIJ, XLLWS, the flux fields and the Stokes drift.  The source terms are evaluated once on fl1 as
+ * it stands -- FKMEAN, ONE SINFLX call (NGST = 2, LLSNEG; UFRIC, Z0M, Z0B, CHRNCK as ff holds them: no TAUT_Z0), and with
+ * LCFLX = LWFLUX .OR. LWFLUXOUT (not IMPLSCH's, which also ORs LWNEMOCOU) SDISSIP, SNONLIN, WNFLUXES (LNUPD = F), FEMEANWS and STOKESTRN --
+ * and nothing is advanced.  Layouts as for ecwam_hip_implsch.
+ *   fl1, wvprpt, ff in (ff's TAUW / TAUWDIR are not touched: STRESSO's are locals of WDFLUXES); mij, xllws out
+ *   intf: with LCFLX, members 2, 3 (USTOKES, VSTOKES) and 5 .. 14 (TAUXD .. PHIAW), with LWFLUX also 0, 1 (WSEMEAN, WSFMEAN) are written;
+ *         without LCFLX nothing is.  intf[ij][15] is the INPUT IBRMEM as for ecwam_hip_implsch.
+ *   wam2nemo: required when LWNEMOCOU (may be NULL otherwise); with LCFLX only its columns 0, 1 (NEMOUSTOKES, NEMOVSTOKES) change, as
+ *             stokestrn.F90:75-88 sets them; without LCFLX nothing does
+ * Served: the configurations the common and the alternate builds of k_implsch4 run (flag sets A and B; IPHYS 0 or ISNONLIN 1 on flag set A).
+ * Double precision at 24 directions is not served (that build gave wrong numbers on the device and is not shipped).
+ * The others (LCIWA2, LWNEMOCOUWRS, LWNEMOCOUSTRN, ISNONLIN 2, ICODE 1 / 2, LWVFLX_SNL = F, the mixed alternates) are refused:
+ * ecwam_hip_wdfluxes_supported returns 1 / 0 and, with 0, leaves the refusal's text in ecwam_hip_last_error.
+ * The call uses the context's rows of ecwam_hip_implsch_reserve, indexed by the point number, as ecwam_hip_implsch does.
+ */
+int ecwam_hip_wdfluxes(ecwam_hip_ctx *ctx, int kijs, int kijl, const void *fl1, const void *wvprpt, const void *ff, void *intf, int *mij,
+                       void *xllws, double *wam2nemo, void *stream);
+int ecwam_hip_wdfluxes_supported(ecwam_hip_ctx *ctx);
+/* SETICE (setice.F90:67-86) on rows [kijs,kijl): where CICOVER = ff[ij][2] > CITHRSH the spectrum becomes
+ * MAX(EPSMIN, 1 - CICOVER) FLMIN MAX(0, COS(TH(K) - WDWAVE))**2; elsewhere it is left as it is.  OUTSTEP0 calls it when LICERUN .AND. LMASKICE.
+ * Refused: fl1 that is not 16-byte aligned (checked for an empty range too), and an NFRE whose reals are no whole number of 16-byte chunks
+ * per direction (NFRE odd in double, no multiple of 4 in single precision): the kernel stores 16 bytes at a time. */
+int ecwam_hip_setice(ecwam_hip_ctx *ctx, int kijs, int kijl, void *fl1, const void *ff, void *stream);
+
+/*
  * One WAMINTGR step with a 1:1 ratio of advection and source-term steps as ONE pass over the spectra (wamintgr.F90:94-146: PROPAG_WAM then
  * IMPLSCH; propag_wam.F90:124-147,247-251,373-400; propags2.F90:99-121): the kernel that integrates the source terms of rows [kijs,kijl)
  * advects them itself while it loads them -- PROPAGS2 (IREFRA = 0, one time step for every frequency, CTU weights rebuilt on the fly from the
