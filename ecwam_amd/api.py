@@ -334,6 +334,27 @@ class HipContext:
         self._chk(self.lib.ecwam_hip_setice(self._h, kijs, kijl, self._real(fl1, (nrow, self.NANG, self.NFRE), "FL1"),
                                             self._real(ff, (ff.shape[0], NFF), "FF"), _stream_ptr()))
 
+    # -- nested grids: BOUINPT / INTSPEC (bouinpt.F90:385-424) and OUTBC (outbc.F90:78-91), the two calls of wamodel.F90:333-343
+    def bouinpt(self, kijs, kijl, ijb, ibcl, ibcr, bfw, f1, par1, fl1, par_out=None):
+        """The coarse model's boundary spectra into the rows ijb (0-based, distinct) of FL1 that lie in [kijs, kijl): ibcl / ibcr = IBFL / IBFR
+        (0 = land, 1 .. nboinp), bfw = BFW; f1 [nboinp][NFRE][NANG] and par1 [nboinp][3] = EMEAN, THQ, FMEAN as the boundary file holds them.
+        par_out [nijb][3] (optional) receives EMEAN, THQ, FMEAN of the result."""
+        nrow, nijb, nboinp = fl1.shape[0], ijb.shape[0], f1.shape[0]
+        if not (0 <= kijs <= kijl <= nrow):
+            raise ValueError("BOUINPT: KIJS/KIJL outside FL1")
+        a = [self._int(ijb, (nijb,), "IJB"), self._int(ibcl, (nijb,), "IBFL"), self._int(ibcr, (nijb,), "IBFR"), self._real(bfw, (nijb,), "BFW"), nboinp,
+             self._real(f1, (nboinp, self.NFRE, self.NANG), "F1"), self._real(par1, (nboinp, 3), "PAR1"), self._real(fl1, (nrow, self.NANG, self.NFRE), "FL1"),
+             None if par_out is None else self._real(par_out, (nijb, 3), "PAR_OUT")]
+        self._chk(self.lib.ecwam_hip_bouinpt(self._h, kijs, kijl, nijb, *a, _stream_ptr()))
+
+    def outbc(self, ijarc, fl1, flpts, par=None):
+        """Rows ijarc (0-based) of FL1 into flpts [nbc][NFRE][NANG] (the order of the boundary file's record) and, unless par is None, their
+        EMEAN, THQ [radians], FMEAN into par [nbc][3]."""
+        nrow, nbc = fl1.shape[0], ijarc.shape[0]
+        a = [self._int(ijarc, (nbc,), "IJARC"), self._real(fl1, (nrow, self.NANG, self.NFRE), "FL1"), self._real(flpts, (nbc, self.NFRE, self.NANG), "FLPTS"),
+             None if par is None else self._real(par, (nbc, 3), "PAR")]
+        self._chk(self.lib.ecwam_hip_outbc(self._h, nbc, *a, _stream_ptr()))
+
     # -- the one-kernel step: PROPAGS2 inside IMPLSCH's tile load (ecwam_hip_propags2_implsch)
     def fused_supported(self, fast_waves: bool = False, obstructions: bool = False) -> bool:
         """The one-kernel step covers the context (and, if asked, its forms with fast-wave sub-steps / sub-grid obstructions)."""

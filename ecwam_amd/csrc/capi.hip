@@ -856,6 +856,34 @@ int ecwam_hip_setice(ecwam_hip_ctx* c, int kijs, int kijl, void* fl1, const void
   return fail("ecwam_hip_setice: the frequencies of a direction are no whole number of 16-byte chunks");
 }
 
+// BOUINPT (bouinpt.F90:385-424 with INTSPEC) and OUTBC (outbc.F90:78-91): the two calls of WAMODEL between the time step and the output
+// (wamodel.F90:333-343); csrc/nest.hip.  They depend on no build of k_implsch4.
+int ecwam_hip_bouinpt(ecwam_hip_ctx* c, int kijs, int kijl, int nijb, const int* ijb, const int* ibcl, const int* ibcr, const void* bfw, int nboinp,
+                      const void* f1, const void* par1, void* fl1, void* par_out, void* stream) {
+  if (!c) return fail("null context");
+  if (nijb < 0 || nboinp < 0) return fail("ecwam_hip_bouinpt: negative count");
+  if (kijl < kijs || kijs < 0) return fail("ecwam_hip_bouinpt: bad range");
+  HIPCHK(hipSetDevice(c->device));
+  if (nijb > 0 && (!ijb || !ibcl || !ibcr || !bfw || !fl1)) return fail("ecwam_hip_bouinpt: null pointer");
+  if (nijb > 0 && nboinp > 0 && (!f1 || !par1)) return fail("ecwam_hip_bouinpt: null pointer (the boundary records)");
+  if (((uintptr_t)fl1 % 16) != 0) return fail("ecwam_hip_bouinpt: the spectra must be 16-byte aligned");
+  const int rc = in_precision(c, [&](auto t) {
+    return launch_bouinpt<decltype(t)>(c->dtab, kijs, kijl, nijb, ijb, ibcl, ibcr, bfw, nboinp, f1, par1, fl1, par_out, c->NANG, c->NFRE, (hipStream_t)stream);
+  });
+  if (rc == 0) return launched();
+  if (rc < 0) return fail("ecwam_hip_bouinpt: the frequencies of a direction are no whole number of 16-byte chunks");
+  return fail("ecwam_hip_bouinpt: unsupported spectral size");
+}
+int ecwam_hip_outbc(ecwam_hip_ctx* c, int nbc, const int* ijarc, const void* fl1, void* flpts, void* par, void* stream) {
+  if (!c) return fail("null context");
+  if (nbc < 0) return fail("ecwam_hip_outbc: negative count");
+  HIPCHK(hipSetDevice(c->device));
+  if (nbc > 0 && (!ijarc || !fl1 || !flpts)) return fail("ecwam_hip_outbc: null pointer");
+  const int rc = in_precision(c, [&](auto t) { return launch_outbc<decltype(t)>(c->dtab, nbc, ijarc, fl1, flpts, par, c->NANG, c->NFRE, (hipStream_t)stream); });
+  if (rc == 0) return launched();
+  return fail("ecwam_hip_outbc: unsupported spectral size");
+}
+
 // bit 0: the one-kernel step covers the context; bit 1: also with fast-wave sub-steps (gin); bit 2: also with the obstructions of
 // ecwam_hip_set_obstructions -- a caller takes the one-kernel step when the bits of what it needs are set
 int ecwam_hip_propags2_implsch_supported(ecwam_hip_ctx* c) { return c && fused_ok(c) ? implsch4_adv_forms(c->NANG, c->real_bytes) : 0; }

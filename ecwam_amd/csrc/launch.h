@@ -96,6 +96,12 @@ const char* so_tab_build(const ecwam_hip_params* p, const void* fr, int real_byt
 void so_coef_layout(int real_bytes, int ND, int AH, int NH, const void* const src[5], std::vector<unsigned char>& host);
 size_t so_work_bytes(int real_bytes, int n, int AH, int NH, int NMAX);
 
+// ---- nest.hip: BOUINPT / INTSPEC and OUTBC (wamodel.F90:333-343).  0 = launched (or nothing to do), 1 = unsupported spectral size, -1 = the frequencies
+// of a direction are no whole number of 16-byte chunks (launch_bouinpt stores 16 bytes at a time, as launch_setice) ---------------------------------
+template <typename T> int launch_bouinpt(const void* tab, int kijs, int kijl, int nijb, const int* ijb, const int* ibcl, const int* ibcr, const void* bfw, int nboinp,
+        const void* f1, const void* par1, void* fl1, void* par_out, int NANG, int NFRE, hipStream_t s);
+template <typename T> int launch_outbc(const void* tab, int nbc, const int* ijarc, const void* fl1, void* flpts, void* par, int NANG, int NFRE, hipStream_t s);
+
 // ---- outblock.hip: OUTBLOCK itself (outblock.F90:159-610) -- the plan of ecwam_hip_set_outblock and the kernel that fills BOUT ---------------------
 // where a BOUT column comes from: the packed buffers of the output calls (in the work space of the context), the caller's per-point arrays, or nothing
 enum { OB_ZERO = 0, OB_W8, OB_SEP, OB_EXT, OB_INT, OB_FF, OB_INTF, OB_UCUR, OB_VCUR, OB_IBRMEM, OB_ALTIM, OB_NEMO, OB_NSRC };

@@ -19,10 +19,10 @@ __device__ __forceinline__ void femean_of_rowsums(const DevTab<T>& tb, T t2, int
 }
 
 // One wavefront per point; sF = the tile [M][NANG|1], complete and visible to the wave.  lane = M sums MAX(F,EPSMIN) over K in the
-// reference's order (FEMEAN), lane = K sums F*DFIM over M in the reference's order (STHQ).  Lane 0 writes o[0..4] = significant wave
-// height, mean direction [degrees], mean period or zmiss, EM, peak period or zmiss.
+// reference's order (FEMEAN), lane = K sums F*DFIM over M in the reference's order (STHQ): EM, FM and THQ [radians, 0 .. 2 PI] in every lane.
+// Shared by outbs_point below and by k_outbc (csrc/nest.hip: the mean parameters of the boundary file's records, outbc.F90:83-84).
 template <typename T>
-__device__ __forceinline__ void outbs_point(const DevTab<T>& tb, const T* sF, int lane, T zmiss, T* __restrict__ o) {
+__device__ __forceinline__ void femean_sthq_point(const DevTab<T>& tb, const T* sF, int lane, T& EM, T& FM, T& THQ) {
   const int NANG = tb.NANG, NFRE = tb.NFRE, NAP = NANG | 1;
   const bool actm = lane < NFRE, actk = lane < NANG;
   // FEMEAN
@@ -32,7 +32,6 @@ __device__ __forceinline__ void outbs_point(const DevTab<T>& tb, const T* sF, in
     t2 = m_max(p[0], tb.EPSMIN);
     for (int kk = 1; kk < NANG; kk++) t2 = t2 + m_max(p[kk], tb.EPSMIN);
   }
-  T EM, FM;
   femean_of_rowsums(tb, t2, lane, EM, FM);
   // STHQ
   T temp = T(0);
@@ -41,8 +40,18 @@ __device__ __forceinline__ void outbs_point(const DevTab<T>& tb, const T* sF, in
   T SI, CI;
   usum2(actk ? tb.SINTH[lane] * temp : T(0), actk ? tb.COSTH[lane] * temp : T(0), SI, CI);
   if (CI == T(0)) CI = tb.EPSMIN;
-  T THQ = m_atan2(SI, CI);
+  THQ = m_atan2(SI, CI);
   if (THQ < T(0)) THQ = THQ + tb.ZPI;
+}
+
+// The same wave and tile.  Lane 0 writes o[0..4] = significant wave height, mean direction [degrees], mean period or zmiss, EM, peak
+// period or zmiss.
+template <typename T>
+__device__ __forceinline__ void outbs_point(const DevTab<T>& tb, const T* sF, int lane, T zmiss, T* __restrict__ o) {
+  const int NANG = tb.NANG, NFRE = tb.NFRE, NAP = NANG | 1;
+  const bool actm = lane < NFRE, actk = lane < NANG;
+  T EM, FM, THQ;
+  femean_sthq_point(tb, sF, lane, EM, FM, THQ);
   // DOMINANT_PERIOD: lane = K finds its maximum, lane = M sums the cropped directions in the reference's order
   T fmx = T(0);
   if (actk)

@@ -597,6 +597,46 @@ class Wamintgr:
         self.fl1[: self.n] = torch.from_numpy(a).to(self.dev)
         self.gfast_valid = False
 
+    # ---- nested grids (wamodel.F90:333-343): the caller sequences step(); bouinpt(); outbc(); outblock() as WAMODEL does.  The tables are the
+    # host's (MBOUNF / MBOUNC): ijb = IJARF and ijarc = IJARC as 0-based local rows, ibcl / ibcr = IBFL / IBFR (0 = land, 1 .. NBOINP), bfw = BFW
+    def set_nest_input(self, ijb, ibcl, ibcr, bfw) -> None:
+        ijb, ibcl, ibcr = (np.ascontiguousarray(a, dtype=np.int32).reshape(-1) for a in (ijb, ibcl, ibcr))
+        bfw = np.ascontiguousarray(bfw, dtype=self.npdt).reshape(-1)
+        if not (ijb.size == ibcl.size == ibcr.size == bfw.size):
+            raise ValueError("set_nest_input: IJB, IBFL, IBFR and BFW differ in length")
+        if ijb.size and (ijb.min() < 0 or ijb.max() >= self.n or np.unique(ijb).size != ijb.size):
+            raise ValueError("set_nest_input: IJB must hold distinct rows this instance owns")
+        if ijb.size and min(ibcl.min(), ibcr.min()) < 0:
+            raise ValueError("set_nest_input: IBFL / IBFR are 0 (land) or 1 .. NBOINP")
+        self._nest_in = tuple(torch.from_numpy(a).to(self.dev) for a in (ijb, ibcl, ibcr, bfw))
+        self._nest_in_max = int(max(ibcl.max(), ibcr.max())) if ijb.size else 0
+
+    def bouinpt(self, f1, par1, par_out=None) -> None:
+        """BOUINPT on self.fl1, on the rows this instance owns: f1 [NBOINP][NFRE][NANG], par1 [NBOINP][3] = EMEAN, THQ, FMEAN (device tensors or arrays)."""
+        if getattr(self, "_nest_in", None) is None:
+            raise RuntimeError("bouinpt: set_nest_input() first")
+        f1, par1 = (a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a, dtype=self.npdt)).to(self.dev) for a in (f1, par1))
+        if f1.shape[0] < self._nest_in_max:
+            raise ValueError(f"bouinpt: IBFL / IBFR reach {self._nest_in_max}, the boundary records hold {f1.shape[0]} points")
+        self.ctx.bouinpt(0, self.n, *self._nest_in, f1, par1, self.fl1, par_out)
+        self.gfast_valid = False
+
+    def set_nest_output(self, ijarc) -> None:
+        ijarc = np.ascontiguousarray(ijarc, dtype=np.int32).reshape(-1)
+        if ijarc.size and (ijarc.min() < 0 or ijarc.max() >= self.n):
+            raise ValueError("set_nest_output: IJARC must hold rows this instance owns")
+        self._nest_out = torch.from_numpy(ijarc).to(self.dev)
+
+    def outbc(self):
+        """OUTBC: (par [NBOUNC][3] = EMEAN, THQ, FMEAN; flpts [NBOUNC][NFRE][NANG]) of the points of set_nest_output()."""
+        if getattr(self, "_nest_out", None) is None:
+            raise RuntimeError("outbc: set_nest_output() first")
+        nbc = self._nest_out.shape[0]
+        par = torch.zeros((nbc, 3), dtype=self.dtype, device=self.dev)
+        flpts = torch.zeros((nbc, self.cfg.nfre, self.cfg.nang), dtype=self.dtype, device=self.dev)
+        self.ctx.outbc(self._nest_out, self.fl1, flpts, par)
+        return par, flpts
+
     # ---- OUTBS subset on the device: [n][5] = swh, mean direction, mean period, EM, peak period; norms = OUTWNORM (avg, min, max, count)
     def outbs(self) -> torch.Tensor:
         out = torch.zeros((self.n, 5), dtype=self.dtype, device=self.dev)

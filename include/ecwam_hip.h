@@ -321,6 +321,37 @@ int ecwam_hip_wdfluxes_supported(ecwam_hip_ctx *ctx);
 int ecwam_hip_setice(ecwam_hip_ctx *ctx, int kijs, int kijl, void *fl1, const void *ff, void *stream);
 
 /*
+ * The two calls of WAMODEL between the time step and the output (wamodel.F90:333-343), for nested (limited-area) runs.  All pointers are
+ * device pointers; both calls work on every context ecwam_hip_create accepts.
+ *
+ * ecwam_hip_bouinpt: BOUINPT's loop over the fine grid's boundary points (bouinpt.F90:385-424): the coarse model's spectra, interpolated
+ * between two coarse boundary points with INTSPEC / ROTSPEC / STRSPEC (Hasselmann's spectrum interpolation), replace the rows of fl1.
+ *   nijb, ijb[nijb]     the boundary points: 0-based rows of fl1.  Only those with kijs <= ijb < kijl are written (the NSTART / NEND test of
+ *                       bouinpt.F90:138-145: a band of a decomposed run passes its own rows); every other row of fl1 is untouched.
+ *                       The entries must be distinct: two entries for one row would race, and the library cannot check a device table.
+ *   ibcl, ibcr [nijb]   IBFL / IBFR: 0 = the land point (spectrum and mean parameters zero; nothing is read for it) or 1 .. nboinp
+ *   bfw[nijb]           BFW, the weight of the right point (DEL12 = 1): <= 0 copies the left spectrum
+ *   f1[nboinp][NFRE][NANG], par1[nboinp][3]
+ *                       the records of the boundary file as it holds them: the spectrum with the direction fastest, and EMEAN, THQ
+ *                       [radians], FMEAN.  Entry i - 1 is index i.
+ *   par_out[nijb][3]    optional (NULL): EMEAN, THQ, FMEAN of the result -- INTSPEC's interpolated values where it ran, the left point's
+ *                       where the spectrum was copied.  Rows of points outside [kijs,kijl) are left alone.
+ * The reference's behaviour is kept, quirks included: the literal 1.1 for the frequency ratio, every frequency up to NFRE written, bins the
+ * loops of STRSPEC do not reach zero, no EPSMIN floor.  Mean frequencies that are zero, negative or not finite give unspecified values at
+ * that point and no access outside the buffers.
+ * Refused: negative counts, kijs > kijl, a null required pointer with nijb > 0, fl1 not 16-byte aligned or an NFRE that does not fill
+ * 16-byte chunks (the rule of ecwam_hip_setice), spectra whose two staged copies do not fit in 64 KiB of LDS.  nijb = 0 launches nothing.
+ *
+ * ecwam_hip_outbc: OUTBC for the coarse model's output boundary points (outbc.F90:78-91): par[nbc][3] = EMEAN (FEMEAN), THQ (STHQ, radians),
+ * FMEAN (FEMEAN) of rows ijarc[nbc] (0-based) of fl1 -- EMEAN the bits of column 3 of ecwam_hip_outbs -- and flpts[nbc][NFRE][NANG] = their
+ * spectra in the order of the file's record.  par may be NULL: a plain gather of point spectra.  The spectral sizes of ecwam_hip_outbs.
+ * Refused: a negative count, a null ijarc / fl1 / flpts with nbc > 0.  nbc = 0 launches nothing.
+ */
+int ecwam_hip_bouinpt(ecwam_hip_ctx *ctx, int kijs, int kijl, int nijb, const int *ijb, const int *ibcl, const int *ibcr, const void *bfw,
+                      int nboinp, const void *f1, const void *par1, void *fl1, void *par_out, void *stream);
+int ecwam_hip_outbc(ecwam_hip_ctx *ctx, int nbc, const int *ijarc, const void *fl1, void *flpts, void *par, void *stream);
+
+/*
  * One WAMINTGR step with a 1:1 ratio of advection and source-term steps as ONE pass over the spectra (wamintgr.F90:94-146: PROPAG_WAM then
  * IMPLSCH; propag_wam.F90:124-147,247-251,373-400; propags2.F90:99-121): the kernel that integrates the source terms of rows [kijs,kijl)
  * advects them itself while it loads them -- PROPAGS2 (IREFRA = 0, one time step for every frequency, CTU weights rebuilt on the fly from the
