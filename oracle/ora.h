@@ -1,13 +1,13 @@
 /*
  * oracle/ora.h -- TEST INFRASTRUCTURE ONLY (CPU oracle for the WAMINTGR hot path).
  *
- * PARITY UNPINNED: the reference (ecmwf-ifs/ecwam 1.5.13) holds no golden vector or
- * known-answer test for IMPLSCH / PROPAGS2 (its only checks are whole-model swh norms that
- * need ETOPO1 + GRIB forcing downloads), and the reference Fortran cannot be built in this
- * image without stand-ins for fiat (PARKIND1, YOMHOOK), generated *.intfb.h and the
- * fypp-generated YOWDRVTYPE.  This file set is therefore a plain-C restatement of the
- * reference algorithm, routine by routine, each function citing the reference file:line
- * it follows.  Nothing under ecwam_amd/ may include, link or call it.
+ * PINNED to the reference's own Fortran (ecmwf-ifs/ecwam 1.5.13): the reference holds no
+ * golden vector or known-answer test for IMPLSCH / PROPAGS2 (its only checks are whole-model
+ * swh norms that need ETOPO1 + GRIB forcing downloads), so this file set is a plain-C
+ * restatement of the reference algorithm, routine by routine, each function citing the
+ * reference file:line it follows -- and tests/test_reference_pin.py holds it to what the
+ * reference's unmodified routines return (oracle/ref_build.py, tests/golden/reference_*.npz;
+ * DESIGN.md section 5).  Nothing under ecwam_amd/ may include, link or call it.
  *
  * Built twice: -DORA_SINGLE (JWRB = float) and default (JWRB = double), mirroring the
  * reference's sp/dp libraries (parkind_wave.F90:23-35).

@@ -1,5 +1,5 @@
 /*
- * oracle/ora_implsch.c -- TEST INFRASTRUCTURE ONLY. See ora.h header ("parity unpinned").
+ * oracle/ora_implsch.c -- TEST INFRASTRUCTURE ONLY. See ora.h header (pinned to the reference: DESIGN.md section 5).
  * Plain-C restatement of the IMPLSCH call tree (implsch.F90 + the routines it inlines),
  * one sea point at a time (the reference's IJ loop is innermost and couples no points).
  * F(k,m) below is FL1(IJ,K,M) of the reference with 0-based k,m.

@@ -1,5 +1,5 @@
 /*
- * oracle/ora_propag.c -- TEST INFRASTRUCTURE ONLY. See ora.h header ("parity unpinned").
+ * oracle/ora_propag.c -- TEST INFRASTRUCTURE ONLY. See ora.h header (pinned to the reference: DESIGN.md section 5).
  * Plain-C restatement of the IPROPAGS=2 advection: CTU weight construction
  * (ctuwupdt.F90, ctuwini.F90, ctuw.F90; spherical grid, ICASE=1, IREFRA=0, LSUBGRID=F => OBS*=1)
  * and the PROPAGS2 stencil (propags2.F90:95-121).

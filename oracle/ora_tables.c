@@ -1,5 +1,5 @@
 /*
- * oracle/ora_tables.c -- TEST INFRASTRUCTURE ONLY. See ora.h header ("parity unpinned").
+ * oracle/ora_tables.c -- TEST INFRASTRUCTURE ONLY. See ora.h header (pinned to the reference: DESIGN.md section 5).
  * Restates the reference's table initialisers (host-side, run once):
  *   iniwcst.F90, mfredir.F90 + mfr.F90, setwavphys.F90, initmdl.F90:436-508, tabu_swellft.F90
  *   (+ kerkei.F90, kzeone.F90), init_x0tauhf.F90, initgc.F90, inisnonlin.F90 + nlweigt.F90 +

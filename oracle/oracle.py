@@ -1,7 +1,7 @@
 """ctypes wrapper of the CPU oracle (oracle/*.c).  TEST INFRASTRUCTURE ONLY.
 
 Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may import this module
-(the product package ecwam_amd never does).  "Parity unpinned": see oracle/ora.h.
+(the product package ecwam_amd never does).  Pinned to the reference's own Fortran by tests/test_reference_pin.py: see oracle/ora.h.
 """
 from __future__ import annotations
 

@@ -2,7 +2,7 @@
 """Writes tests/golden/oracle_regression_dp.npz: outputs of THIS repository's CPU oracle (double precision) for small seeded
 cases of IMPLSCH (flag set A, flag set B, sea-ice attenuation) and of CTUW + PROPAGS2 (plain and with currents).  These are
 regression vectors -- they freeze the oracle's behaviour so that a later edit cannot change it unnoticed; they are NOT outputs
-of the reference (which cannot be built here) and pin nothing against it."""
+of the reference and pin nothing against it (what does: tests/test_reference_pin.py)."""
 import os
 import sys
 

@@ -98,6 +98,17 @@ def test_product_never_imports_oracle():
             if f.endswith((".py", ".hip", ".h", ".cpp", ".F90")):
                 txt = open(os.path.join(dirpath, f)).read()
                 assert "oracle" not in txt.replace("test oracle", "").lower() or f in ("lib.py",), (dirpath, f)
+                for word in ("ref_build", "libecwam_ref", "ref_driver", "_ref/"):      # the reference's own Fortran (oracle/_ref/): the checker's checker
+                    assert word not in txt, (dirpath, f, word)
+    # bench.py and smoke() may use the oracle (CPU baseline, the smoke check) but never the reference libraries: they exist only where a
+    # reference tree does
+    import inspect
+
+    import __graft_entry__ as entry
+
+    for what, txt in (("bench.py", open(os.path.join(ROOT, "bench.py")).read()), ("smoke()", inspect.getsource(entry.smoke))):
+        for word in ("oracle.reference", "oracle import reference", "ref_build", "libecwam_ref", "Reference("):
+            assert word not in txt, (what, word)
 
 
 def test_product_never_touches_the_tests_second_implementation():
