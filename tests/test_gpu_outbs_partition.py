@@ -228,6 +228,34 @@ def test_wamintgr_on_the_o48_grid(api, prec):
     m.ctx.close()
 
 
+@pytest.mark.parametrize("prec", ["sp", "dp"])
+@pytest.mark.parametrize("nang,nfre", [(12, 36), (24, 36), (36, 36), (48, 36), (12, 25)])
+def test_first_15_columns_are_outbs_sepwisw_bit_for_bit(api, prec, nang, nfre):
+    """The two builds of the one SEPWISW kernel (LLPARTITION = F / T) give the same bits in the columns they share: at every direction
+    count, with the NFRE_ODD tail of an odd NFRE, and with a partial last workgroup (the 64 rows [3, 67) start off a workgroup boundary of
+    the array, and 67 is no multiple of the 4 or 2 waves of a workgroup).  Inputs after IMPLSCH as in test_parity_after_implsch; IMPLSCH
+    covers 36 frequencies only, so 12 x 25 takes the inputs of test_parity_12x25."""
+    n, a = 67, 3
+    if nfre == 36:
+        ctx, t, fl1, xl, mij, wv, ff = _implsch_case(api, Config(nang=nang, nfre=nfre, nfre_red=nfre), prec, n, seed=17)
+    else:
+        from test_outbs_partition_host import multi_system_case
+
+        t = Tables(Config(nang=nang, nfre=nfre, nfre_red=nfre), H.np_dtype(prec))
+        ctx = api.HipContext(t)
+        fl1, xl, mij, cinv, uf, wd = multi_system_case(t, n, seed=23)
+        wv, ff = _point_inputs(t, fl1, xl, mij, cinv, uf, wd)
+    part = _run(api, ctx, fl1, xl, mij, wv, ff, kijs=a, kijl=n)
+    tfl, txl, twv, tff = _device(ctx, fl1, xl, wv, ff)
+    sep = torch.full((n, 15), -1.0, dtype=ctx.dtype, device=ctx.device)
+    ctx.outbs_sepwisw(a, n, tfl, txl, twv, tff, sep)
+    torch.cuda.synchronize()
+    assert torch.equal(torch.from_numpy(part[a:, :15]), sep[a:].cpu())
+    assert (part[a:, 3:5] > 0).any()                                            # heights of the parts: the rows were written
+    assert np.all(part[:a] == -1.0) and bool(torch.all(sep[:a] == -1.0))        # rows outside [kijs, kijl) untouched
+    ctx.close()
+
+
 def test_rows_beyond_2_32_elements(api):
     """64-bit row addressing: FL1 / XLLWS with just over 2**32 / (NANG NFRE) rows; a case in the last 64 rows gives what it gives at row 0."""
     cfg = Config(nang=36, nfre=36, nfre_red=36)

@@ -117,7 +117,7 @@ def main() -> None:
     s = np.dtype(dt).itemsize
     nbytes = n * ((2 * K * M + M + 3 + 24) * s + 4)
     med = float(np.median(times))
-    print(json.dumps(dict(kernel="k_outbs_partition", prec=a.prec, worst=a.worst, npts=n, iters=a.iters, median_s=med, min_s=float(np.min(times)),
+    print(json.dumps(dict(kernel=f"k_outbs_sepwisw<{'float' if a.prec == 'sp' else 'double'}, true>", prec=a.prec, worst=a.worst, npts=n, iters=a.iters, median_s=med, min_s=float(np.min(times)),
                           max_s=float(np.max(times)), bytes=nbytes, bytes_per_s=nbytes / med, hbm_peak_share=nbytes / med / HBM_PEAK,
                           trains_per_point=np.bincount(ntr, minlength=4).tolist())))
     ctx.close()

@@ -71,7 +71,7 @@ def main() -> None:
     s = np.dtype(dt).itemsize
     nbytes = n * (2 * K * M + M + 3 + 15) * s
     med = float(np.median(times))
-    print(json.dumps(dict(kernel="k_outbs_sepwisw", prec=a.prec, npts=n, iters=a.iters, median_s=med, min_s=float(np.min(times)),
+    print(json.dumps(dict(kernel=f"k_outbs_sepwisw<{'float' if a.prec == 'sp' else 'double'}, false>", prec=a.prec, npts=n, iters=a.iters, median_s=med, min_s=float(np.min(times)),
                           max_s=float(np.max(times)), bytes=nbytes, bytes_per_s=nbytes / med, hbm_peak_share=nbytes / med / HBM_PEAK)))
     ctx.close()
 
