@@ -334,6 +334,36 @@ class HipContext:
         self._chk(self.lib.ecwam_hip_setice(self._h, kijs, kijl, self._real(fl1, (nrow, self.NANG, self.NFRE), "FL1"),
                                             self._real(ff, (ff.shape[0], NFF), "FF"), _stream_ptr()))
 
+    # -- the start spectra (include/ecwam_hip_start.h; csrc/start.hip): what creates FL1 where a run does not begin from a restart file
+    def _start_rows(self, who, kijs, kijl, fl1, ff=None):
+        nrow = fl1.shape[0]
+        if not (0 <= kijs <= kijl <= (nrow if ff is None else min(nrow, ff.shape[0]))):
+            raise ValueError(f"{who}: KIJS/KIJL outside the operands")
+        a = [self._real(fl1, (nrow, self.NANG, self.NFRE), "FL1")]
+        return a if ff is None else a + [self._real(ff, (ff.shape[0], NFF), "FF")]
+
+    def mstart(self, kijs, kijl, fl1, ff, iopti, fetch, frmax, thetaq, fm, alfa, zgamma, sa, sb):
+        """MSTART (mstart.F90:104-136) for IOPTI 0, 1, 2 on rows [kijs, kijl): FL1 is written from WSWAVE and WDWAVE of FF and MSTART's eight
+        reals (the fetch in metres, the maximum peak frequency, the mean direction in radians, FM, ALFA, ZGAMMA, SA, SB)."""
+        self._chk(self.lib.ecwam_hip_mstart(self._h, kijs, kijl, *self._start_rows("MSTART", kijs, kijl, fl1, ff), int(iopti),
+                                            *(float(v) for v in (fetch, frmax, thetaq, fm, alfa, zgamma, sa, sb)), _stream_ptr()))
+
+    def unsetice(self, kijs, kijl, fl1, ff, delphi, restarted: bool = False, small_domain: bool = False):
+        """UNSETICE (unsetice.F90:79-171) on rows [kijs, kijl); delphi = DELPHI [m].  restarted / small_domain are LRESTARTED and CLDOMAIN == 's':
+        with either the routine does nothing (unsetice.F90:79) and nothing is launched."""
+        self._chk(self.lib.ecwam_hip_unsetice(self._h, kijs, kijl, *self._start_rows("UNSETICE", kijs, kijl, fl1, ff), float(delphi),
+                                              (1 if restarted else 0) | (2 if small_domain else 0), _stream_ptr()))
+
+    def getspec_noise(self, kijs, kijl, fl1):
+        """GETSPEC's noise start (getspec.F90:174-188): FL1 = EPSMIN on rows [kijs, kijl)."""
+        self._chk(self.lib.ecwam_hip_getspec_noise(self._h, kijs, kijl, *self._start_rows("GETSPEC", kijs, kijl, fl1), _stream_ptr()))
+
+    def getspec_tail(self, kijs, kijl, fl1, ff, nfre_red=None):
+        """The end of GETSPEC's GRIB read (getspec.F90:648-659) on rows [kijs, kijl): the frequencies above nfre_red (default: the context's
+        NFRE_RED) from the last one read, then SDEPTHLIM with EMAXDPT of FF."""
+        self._chk(self.lib.ecwam_hip_getspec_tail(self._h, kijs, kijl, *self._start_rows("GETSPEC", kijs, kijl, fl1, ff),
+                                                  int(self.NR if nfre_red is None else nfre_red), _stream_ptr()))
+
     # -- nested grids: BOUINPT / INTSPEC (bouinpt.F90:385-424) and OUTBC (outbc.F90:78-91), the two calls of wamodel.F90:333-343
     def bouinpt(self, kijs, kijl, ijb, ibcl, ibcr, bfw, f1, par1, fl1, par_out=None):
         """The coarse model's boundary spectra into the rows ijb (0-based, distinct) of FL1 that lie in [kijs, kijl): ibcl / ibcr = IBFL / IBFR

@@ -9,6 +9,7 @@
 #include <dlfcn.h>
 #include <rccl/rccl.h>   // types and prototypes only: librccl is loaded with dlopen when a communicator is asked for
 
+#include "../../include/ecwam_hip_start.h"
 #include "dev.h"
 #include "launch.h"
 
@@ -882,6 +883,55 @@ int ecwam_hip_outbc(ecwam_hip_ctx* c, int nbc, const int* ijarc, const void* fl1
   const int rc = in_precision(c, [&](auto t) { return launch_outbc<decltype(t)>(c->dtab, nbc, ijarc, fl1, flpts, par, c->NANG, c->NFRE, (hipStream_t)stream); });
   if (rc == 0) return launched();
   return fail("ecwam_hip_outbc: unsupported spectral size");
+}
+
+// The start spectra (include/ecwam_hip_start.h; csrc/start.hip): MSTART, UNSETICE, GETSPEC's noise start and tail.  The checks every one of
+// them makes, in the order of ecwam_hip_setice; 0 = go on
+static int start_checks(ecwam_hip_ctx* c, const char* who, int kijs, int kijl, const void* fl1, const void* ff, bool reads_ff) {
+  if (kijl < kijs || kijs < 0) return fail(std::string(who) + ": bad range");
+  HIPCHK(hipSetDevice(c->device));
+  if (kijl > kijs && (!fl1 || (reads_ff && !ff))) return fail(std::string(who) + ": null pointer");
+  if (((uintptr_t)fl1 % 16) != 0) return fail(std::string(who) + ": the spectra must be 16-byte aligned");
+  return 0;
+}
+static int start_done(const char* who, int rc) {
+  if (rc == 0) return launched();
+  if (rc < 0) return fail(std::string(who) + ": the frequencies of a direction are no whole number of 16-byte chunks");
+  return fail(std::string(who) + ": unsupported spectral size");
+}
+int ecwam_hip_mstart(ecwam_hip_ctx* c, int kijs, int kijl, void* fl1, const void* ff, int iopti, double fetch, double frmax, double thetaq, double fm,
+                     double alfa, double zgamma, double sa, double sb, void* stream) {
+  if (!c) return fail("null context");
+  if (int rc = start_checks(c, "ecwam_hip_mstart", kijs, kijl, fl1, ff, true)) return rc;
+  if (iopti < 0 || iopti > 2) return fail("ecwam_hip_mstart: IOPTI must be 0, 1 or 2 (IOPTI = 3, MSWELL, reads a gridded field and is not served)");
+  const double par[8] = {fetch, frmax, thetaq, fm, alfa, zgamma, sa, sb};
+  return start_done("ecwam_hip_mstart", in_precision(c, [&](auto t) {
+    return launch_mstart<decltype(t)>(c->dtab, kijs, kijl, fl1, ff, iopti, par, c->NANG, c->NFRE, (hipStream_t)stream);
+  }));
+}
+int ecwam_hip_unsetice(ecwam_hip_ctx* c, int kijs, int kijl, void* fl1, const void* ff, double delphi, int flags, void* stream) {
+  if (!c) return fail("null context");
+  if (int rc = start_checks(c, "ecwam_hip_unsetice", kijs, kijl, fl1, ff, true)) return rc;
+  if (flags & ~3) return fail("ecwam_hip_unsetice: unknown flags");
+  if (flags) return 0;      // LRESTARTED, or CLDOMAIN == 's': unsetice.F90:79 skips the routine
+  return start_done("ecwam_hip_unsetice", in_precision(c, [&](auto t) {
+    return launch_unsetice<decltype(t)>(c->dtab, kijs, kijl, fl1, ff, delphi, c->p.licerun && c->p.lmaskice, c->p.lbiwbk != 0, c->NANG, c->NFRE, (hipStream_t)stream);
+  }));
+}
+int ecwam_hip_getspec_noise(ecwam_hip_ctx* c, int kijs, int kijl, void* fl1, void* stream) {
+  if (!c) return fail("null context");
+  if (int rc = start_checks(c, "ecwam_hip_getspec_noise", kijs, kijl, fl1, nullptr, false)) return rc;
+  return start_done("ecwam_hip_getspec_noise", in_precision(c, [&](auto t) {
+    return launch_getspec_noise<decltype(t)>(c->dtab, kijs, kijl, fl1, c->NANG, c->NFRE, (hipStream_t)stream);
+  }));
+}
+int ecwam_hip_getspec_tail(ecwam_hip_ctx* c, int kijs, int kijl, void* fl1, const void* ff, int nfre_red, void* stream) {
+  if (!c) return fail("null context");
+  if (int rc = start_checks(c, "ecwam_hip_getspec_tail", kijs, kijl, fl1, ff, true)) return rc;
+  if (nfre_red < 1 || nfre_red > c->NFRE) return fail("ecwam_hip_getspec_tail: nfre_red outside 1 .. NFRE");
+  return start_done("ecwam_hip_getspec_tail", in_precision(c, [&](auto t) {
+    return launch_getspec_tail<decltype(t)>(c->dtab, kijs, kijl, fl1, ff, nfre_red, c->NANG, c->NFRE, (hipStream_t)stream);
+  }));
 }
 
 // bit 0: the one-kernel step covers the context; bit 1: also with fast-wave sub-steps (gin); bit 2: also with the obstructions of

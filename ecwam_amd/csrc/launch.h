@@ -102,6 +102,15 @@ template <typename T> int launch_bouinpt(const void* tab, int kijs, int kijl, in
         const void* f1, const void* par1, void* fl1, void* par_out, int NANG, int NFRE, hipStream_t s);
 template <typename T> int launch_outbc(const void* tab, int nbc, const int* ijarc, const void* fl1, void* flpts, void* par, int NANG, int NFRE, hipStream_t s);
 
+// ---- start.hip: the start spectra -- MSTART (IOPTI 0, 1, 2; par = FETCH, FRMAX, THETAQ, FM, ALFA, ZGAMMA, SA, SB), UNSETICE (cimask: LICERUN .AND. LMASKICE,
+// lim: LBIWBK), GETSPEC's noise start and tail.  0 = launched (or nothing to do), 1 = unsupported spectral size, -1 = the frequencies of a direction are
+// no whole number of 16-byte chunks (as launch_setice) ------------------------------------------------------------------------------------------------
+template <typename T> int launch_mstart(const void* tab, int kijs, int kijl, void* fl1, const void* ff, int iopti, const double* par, int NANG, int NFRE, hipStream_t s);
+template <typename T> int launch_unsetice(const void* tab, int kijs, int kijl, void* fl1, const void* ff, double delphi, int cimask, int lim, int NANG, int NFRE,
+        hipStream_t s);
+template <typename T> int launch_getspec_noise(const void* tab, int kijs, int kijl, void* fl1, int NANG, int NFRE, hipStream_t s);
+template <typename T> int launch_getspec_tail(const void* tab, int kijs, int kijl, void* fl1, const void* ff, int nfre_red, int NANG, int NFRE, hipStream_t s);
+
 // ---- outblock.hip: OUTBLOCK itself (outblock.F90:159-610) -- the plan of ecwam_hip_set_outblock and the kernel that fills BOUT ---------------------
 // where a BOUT column comes from: the packed buffers of the output calls (in the work space of the context), the caller's per-point arrays, or nothing
 enum { OB_ZERO = 0, OB_W8, OB_SEP, OB_EXT, OB_INT, OB_FF, OB_INTF, OB_UCUR, OB_VCUR, OB_IBRMEM, OB_ALTIM, OB_NEMO, OB_NSRC };

@@ -63,6 +63,9 @@ EXPORTS = ["ecwam_hip_last_error", "ecwam_hip_abi_version", "ecwam_hip_selftest"
            "ecwam_hip_memcpy_h2d", "ecwam_hip_memcpy_d2h", "ecwam_hip_memset", "ecwam_hip_sync", "ecwam_hip_queue_create", "ecwam_hip_queue_destroy",
            "ecwam_hip_queue_wait_for"]
 
+# include/ecwam_hip_start.h: the start spectra, added to ABI 6 in a header and a list of their own (EXPORTS is the list of include/ecwam_hip.h)
+EXPORTS_START = ["ecwam_hip_mstart", "ecwam_hip_unsetice", "ecwam_hip_getspec_noise", "ecwam_hip_getspec_tail"]
+
 ABI_VERSION = 6        # include/ecwam_hip.h ECWAM_HIP_ABI_VERSION
 _lib = None
 
@@ -149,6 +152,12 @@ def load() -> C.CDLL:
     lib.ecwam_hip_halo_unpack_host.argtypes = [vp, vp, ci, vp, vp]
     lib.ecwam_hip_proenvhalo_pack.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp, vp]
     lib.ecwam_hip_proenvhalo_unpack.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    for name in EXPORTS_START:
+        getattr(lib, name).restype = C.c_int
+    lib.ecwam_hip_mstart.argtypes = [vp, ci, ci, vp, vp, ci, cd, cd, cd, cd, cd, cd, cd, cd, vp]
+    lib.ecwam_hip_unsetice.argtypes = [vp, ci, ci, vp, vp, cd, ci, vp]
+    lib.ecwam_hip_getspec_noise.argtypes = [vp, ci, ci, vp, vp]
+    lib.ecwam_hip_getspec_tail.argtypes = [vp, ci, ci, vp, vp, ci, vp]
     _lib = lib
     return lib
 

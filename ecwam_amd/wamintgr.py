@@ -597,6 +597,39 @@ class Wamintgr:
         self.fl1[: self.n] = torch.from_numpy(a).to(self.dev)
         self.gfast_valid = False
 
+    # ---- the start spectra on the device-resident FL1 and FF, over the local rows (csrc/start.hip): a run that does not begin from a restart file
+    def delphi(self) -> float:
+        """DELPHI, the latitude increment in metres (readmdlconf.F90:136: XDELLA CIRC / 360)"""
+        return float(self.grid.xdella) * float(self.t.CIRC) / 360.0
+
+    def cold_start(self, iopti: int = 1, fetch: float = 0.0, fm: float = 0.0, alfa: float = 0.0, gamma: float = 0.0, sa: float = 0.0, sb: float = 0.0,
+                   theta: float = 0.0) -> None:
+        """preset's cold start (preset.F90:618-638): MSTART on every local row from WSWAVE and WDWAVE of FF.  The defaults are preset's namelist
+        defaults (preset.F90:237, 240-246: IOPTI = 1, ALFA = FM = GAMMA = SA = SB = THETA = FETCH = 0): as there, a run sets what its option
+        reads.  theta is in degrees (THETAQ = THETA RAD, preset.F90:631), a fetch below 0.1E-5 becomes 0.5 DELPHI (preset.F90:618) and
+        FRMAX = FM (preset.F90:619).  IOPTI = 3 is refused."""
+        if fetch < 0.1e-5:
+            fetch = 0.5 * self.delphi()
+        self.ctx.mstart(0, self.n, self.fl1, self.ff, iopti, fetch, fm, theta * float(self.t.RAD), fm, alfa, gamma, sa, sb)
+        self.gfast_valid = False
+
+    def noise_start(self) -> None:
+        """GETSPEC's LNSESTART (getspec.F90:174-188): FL1 = EPSMIN."""
+        self.ctx.getspec_noise(0, self.n, self.fl1)
+        self.gfast_valid = False
+
+    def getspec_tail(self, nfre_red: int | None = None) -> None:
+        """The end of GETSPEC's GRIB read (getspec.F90:648-659) on the spectra as they stand: the frequencies above nfre_red (default NFRE_RED)
+        filled, then SDEPTHLIM."""
+        self.ctx.getspec_tail(0, self.n, self.fl1, self.ff, nfre_red)
+        self.gfast_valid = False
+
+    def unsetice(self, delphi: float | None = None, restarted: bool = False, small_domain: bool = False) -> None:
+        """UNSETICE (unsetice.F90:79-171) as INITMDL calls it on every chunk (initmdl.F90:1024-1037); delphi defaults to the grid's."""
+        self.ctx.unsetice(0, self.n, self.fl1, self.ff, self.delphi() if delphi is None else delphi, restarted, small_domain)
+        if not (restarted or small_domain):
+            self.gfast_valid = False
+
     # ---- nested grids (wamodel.F90:333-343): the caller sequences step(); bouinpt(); outbc(); outblock() as WAMODEL does.  The tables are the
     # host's (MBOUNF / MBOUNC): ijb = IJARF and ijarc = IJARC as 0-based local rows, ibcl / ibcr = IBFL / IBFR (0 = land, 1 .. NBOINP), bfw = BFW
     def set_nest_input(self, ijb, ibcl, ibcr, bfw) -> None:
