@@ -11,6 +11,7 @@
 
 #include "../../include/ecwam_hip_start.h"
 #include "dev.h"
+#include "implsch_v4_shapes.h"
 #include "launch.h"
 
 static thread_local std::string g_err;
@@ -492,8 +493,7 @@ int ecwam_hip_create(const ecwam_hip_params* p, const ecwam_hip_tables* t, int r
   // IMPLSCH runs k_implsch4 (implsch_v4.h) and nothing else since round 5: refuse here what its builds do not cover, with the reason
   {
     const char* why = nullptr;
-    const bool inst = (c->NANG == 48 && c->v4_r1 == 1 && c->v4_r2 == 4 && c->v4_nh == 11) || (c->NANG == 36 && c->v4_r1 == 1 && c->v4_r2 == 3 && c->v4_nh == 8) ||
-                      (c->NANG == 24 && c->v4_r1 == 0 && c->v4_r2 == 2 && c->v4_nh == 5) || (c->NANG == 12 && c->v4_r1 == 0 && c->v4_r2 == 1 && c->v4_nh == 3);
+    const bool inst = v4_for_shape(c->NANG, c->v4_r1, c->v4_r2, c->v4_nh, [](auto) { return 0; }) == 0;      // (implsch_v4_shapes.h)
     if (p->nfre != 36) why = "NFRE must be 36 (the frequency grid of every configuration of the reference)";
     else if (!c->v4_ok) why = "the saturation weights / indices do not have the structure of INIT_SDISS_ARDH (COS**2 taps, symmetric, the same for every direction) or the DIA mirror images differ";
     else if (!inst) why = "NANG must be 48, 36, 24 or 12 with the interaction rotations and the saturation half-width of INISNONLIN / INIT_SDISS_ARDH on that grid";
@@ -718,25 +718,27 @@ int ecwam_hip_propags2_refra(ecwam_hip_ctx* c, const void* f1, void* f3, int n, 
                              copy_rest ? 1 : 0, (hipStream_t)stream);
 }
 
-// The build of k_implsch4 (implsch_v4.h) a context runs.  The common builds (implsch4.hip): flag sets A and B (ext: LLGCBZ0, LLNORMAGAM), with
-// or without the sea-ice damping rates that depend on the frequency only (LCIWA1, LCIWA3, LCISCAL).  The alternate builds (implsch4x.hip), on
-// flag set A only: alt = 1 IPHYS 0 (sinput_jan + sdissip_jan; its TAUWSHELTER is 0), alt = 2 ISNONLIN 1 (TRANSF per interaction frequency) --
-// what the reference's registered configurations select.  Everything else runs the RARE builds (implsch4r.hip: LCIWA2, the NEMO ice stress
-// and strain, ISNONLIN 2, ICODE 1 / 2, LWVFLX_SNL = F, ISNONLIN 1 beside flag set B or IPHYS 0, IPHYS 0 beside flag set B).  ecwam_hip_create
-// has refused what no build covers.
-enum class Implsch4Build { common, alternate, rare };
-struct Implsch4Choice { Implsch4Build build; int ext, alt; };
-static Implsch4Choice implsch4_choice(const ecwam_hip_ctx* c) {
-  const int ext = (c->p.llnormagam || c->p.llgcbz0) ? 1 : 0;
+// The variant of k_implsch4 (implsch_v4.h; launch.h: Implsch4Variant) a context runs.  The common builds (implsch4.hip): flag sets A and B
+// (LLGCBZ0, LLNORMAGAM), with or without the sea-ice damping rates that depend on the frequency only (LCIWA1, LCIWA3, LCISCAL).  The alternate
+// builds (implsch4x.hip), on flag set A only: IPHYS 0 (sinput_jan + sdissip_jan; its TAUWSHELTER is 0), ISNONLIN 1 (TRANSF per interaction
+// frequency) -- what the reference's registered configurations select.  Everything else runs the RARE builds (implsch4r.hip: LCIWA2, the NEMO
+// ice stress and strain, ISNONLIN 2, ICODE 1 / 2, LWVFLX_SNL = F, ISNONLIN 1 beside flag set B or IPHYS 0, IPHYS 0 beside flag set B).
+// ecwam_hip_create has refused what no build covers.
+static Implsch4Variant implsch4_variant(const ecwam_hip_ctx* c) {
+  const bool ext = c->p.llnormagam || c->p.llgcbz0, jan = c->p.iphys == 0, enhmc = c->p.isnonlin == 1;
   const bool rare4 = c->p.lciwa2 || c->p.lwnemocouwrs || c->p.lwnemocoustrn || c->p.isnonlin > 1 || c->p.icode != 3 || !c->p.lwvflx_snl;
-  const int alt = (c->p.iphys == 0 ? 1 : 0) | (c->p.isnonlin == 1 ? 2 : 0);
-  if (rare4 || (alt != 0 && (ext || alt == 3))) return {Implsch4Build::rare, ext, alt};
-  return {alt ? Implsch4Build::alternate : Implsch4Build::common, ext, alt};
+  if (rare4 || ((jan || enhmc) && (ext || (jan && enhmc)))) return jan ? Implsch4Variant::rare_iphys0 : Implsch4Variant::rare;
+  return jan ? Implsch4Variant::iphys0 : enhmc ? Implsch4Variant::isnonlin1 : ext ? Implsch4Variant::B : Implsch4Variant::A;
+}
+static bool implsch4_rare(const ecwam_hip_ctx* c) {
+  const Implsch4Variant v = implsch4_variant(c);
+  return v == Implsch4Variant::rare || v == Implsch4Variant::rare_iphys0;
 }
 // the configurations the one-kernel step covers (implsch4a.hip: the common builds on IPHYS 1, ISNONLIN 0); everything else runs
 // ecwam_hip_propags2_otf + ecwam_hip_implsch
 static bool fused_ok(const ecwam_hip_ctx* c) {
-  return c->implsch_why.empty() && implsch4_choice(c).build == Implsch4Build::common && c->NFRE == 36;      // (the direction count: one of k_implsch4's, checked at create)
+  const Implsch4Variant v = implsch4_variant(c);
+  return c->implsch_why.empty() && (v == Implsch4Variant::A || v == Implsch4Variant::B) && c->NFRE == 36;      // (the direction count: one of k_implsch4's, checked at create)
 }
 // The tables the one-kernel step takes its CTU scalars from (k_ctu_prep fills them every call): sized with the fin rows, so that a host that
 // called ecwam_hip_implsch_reserve has no allocation in its time loop on this path either.  Contexts without a one-kernel build hold none.
@@ -771,7 +773,7 @@ static int implsch_reserve_on(ecwam_hip_ctx* c, int npts, hipStream_t s) {
   // the split kernel pair parks the wind-input coefficient of every bin between its two halves: a double precision context whose
   // configuration runs the RARE builds (implsch4r.hip: their dp form is the split) -- NOT every double precision context: the rows are a
   // fourth spectrum-sized array (68 GB at O1280)
-  const bool split = c->real_bytes == 8 && implsch4_choice(c).build == Implsch4Build::rare;
+  const bool split = c->real_bytes == 8 && implsch4_rare(c);
   const size_t need_wi = split ? (size_t)(npts > 0 ? npts : 0) * c->NANG * c->NFRE * c->real_bytes : 0;
   if (need_wi > c->wi_bytes) {
     if (c->wi) HIPCHK(hipFree(c->wi));
@@ -792,14 +794,14 @@ int ecwam_hip_implsch(ecwam_hip_ctx* c, int kijs, int kijl, void* fl1, const voi
   hipStream_t s = (hipStream_t)stream;
   if (!c->implsch_why.empty()) return fail("ecwam_hip_implsch: " + c->implsch_why);
   if (dbg) return fail("ecwam_hip_implsch: the per-point debug rows were an output of the retired one-point-per-wavefront kernel: pass NULL");
-  const Implsch4Choice b = implsch4_choice(c);
+  const Implsch4Variant v = implsch4_variant(c);
   if (int rc2 = implsch_reserve_on(c, kijl, s)) return rc2;   // no-op once the buffer covers kijl
   const int rc = in_precision(c, [&](auto t) {
     using T = decltype(t);
-    const bool rare = b.build == Implsch4Build::rare, alt = b.build == Implsch4Build::alternate;
-    const auto launch = rare ? launch_implsch4r<T> : alt ? launch_implsch4x<T> : launch_implsch4<T>;
+    const bool alt = v == Implsch4Variant::iphys0 || v == Implsch4Variant::isnonlin1;
+    const auto launch = implsch4_rare(c) ? launch_implsch4r<T> : alt ? launch_implsch4x<T> : launch_implsch4<T>;
     return launch(c->dtab, kijs, kijl, fl1, wvprpt, ff, intf, mij, xllws, c->fin, wam2nemo, c->fast_g, c->fast_gk, c->wi, c->NANG, c->NFRE, c->v4_r1, c->v4_r2,
-                  c->v4_nh, rare ? (c->p.iphys == 0 ? 1 : 0) : alt ? b.alt : b.ext, s);
+                  c->v4_nh, v, s);
   });
   if (rc == 0) { HIPCHK(hipGetLastError()); c->implsch_last = 4; return 0; }
   return fail("ecwam_hip_implsch: no build of k_implsch4 covers the configuration (ecwam_hip_create should have refused it)");
@@ -807,11 +809,9 @@ int ecwam_hip_implsch(ecwam_hip_ctx* c, int kijs, int kijl, void* fl1, const voi
 
 // WDFLUXES: the switch of a RARE configuration that keeps it from this call (the common and the alternate builds have the mode), or NULL
 static const char* wdfluxes_uncovered(const ecwam_hip_ctx* c) {
-  // (the double precision build at 24 directions computed wrong fluxes on the device: implsch4w.hip does not instantiate it)
-#ifndef ECWAM_HIP_WDF_DP24
-  if (c->NANG == 24 && c->real_bytes == 8) return "24 directions in double precision";
-#endif
-  if (implsch4_choice(c).build != Implsch4Build::rare) return nullptr;
+  // (the double precision build at 24 directions computed wrong fluxes on the device: implsch4w.hip does not instantiate it, and says so here)
+  if (!wdfluxes_built(c->NANG, c->real_bytes)) return "24 directions in double precision";
+  if (!implsch4_rare(c)) return nullptr;
   if (c->p.lciwa2) return "LCIWA2";
   if (c->p.lwnemocouwrs) return "LWNEMOCOUWRS";
   if (c->p.lwnemocoustrn) return "LWNEMOCOUSTRN";
@@ -837,11 +837,10 @@ int ecwam_hip_wdfluxes(ecwam_hip_ctx* c, int kijs, int kijl, const void* fl1, co
   hipStream_t s = (hipStream_t)stream;
   if (!c->implsch_why.empty()) return fail("ecwam_hip_wdfluxes: " + c->implsch_why);
   if (const char* w = wdfluxes_uncovered(c)) return fail(std::string("ecwam_hip_wdfluxes: not covered: ") + w);
-  const Implsch4Choice b = implsch4_choice(c);
   if (int rc2 = implsch_reserve_on(c, kijl, s)) return rc2;   // no-op once the buffer covers kijl
-  const int sel = b.build == Implsch4Build::alternate ? (b.alt == 1 ? 2 : 3) : b.ext;
+  const Implsch4Variant v = implsch4_variant(c);
   const int rc = in_precision(c, [&](auto t) {
-    return launch_wdfluxes<decltype(t)>(c->dtab, kijs, kijl, fl1, wvprpt, ff, intf, mij, xllws, c->fin, wam2nemo, c->NANG, c->NFRE, c->v4_r1, c->v4_r2, c->v4_nh, sel, s);
+    return launch_wdfluxes<decltype(t)>(c->dtab, kijs, kijl, fl1, wvprpt, ff, intf, mij, xllws, c->fin, wam2nemo, c->NANG, c->NFRE, c->v4_r1, c->v4_r2, c->v4_nh, v, s);
   });
   if (rc == 0) { HIPCHK(hipGetLastError()); return 0; }
   return fail("ecwam_hip_wdfluxes: no build of k_implsch4 covers the configuration (ecwam_hip_create should have refused it)");
@@ -976,10 +975,10 @@ int ecwam_hip_propags2_implsch(ecwam_hip_ctx* c, const void* f1, void* f3, int n
   a.gin = gin; a.delpro_lf = dlf; a.gin_k = gin ? gin_nfre : 0; a.mlf = gin ? ifrelfmax : 0;
   a.obs = c->obs;      // ecwam_hip_set_obstructions (LSUBGRID)
   a.gfast = c->fast_g; a.gfast_k = c->fast_g ? c->fast_gk : 0;      // ecwam_hip_set_fastwave_copy, as for ecwam_hip_implsch
-  const int ext = implsch4_choice(c).ext;
+  const Implsch4Variant v = implsch4_variant(c);
   const int rc = in_precision(c, [&](auto t) {
     return launch_implsch4_adv<decltype(t)>(c->dtab, kijs, kijl, f3, wvprpt, ff, intf, mij, xllws, c->fin, wam2nemo, &a, c->NANG, c->NFRE, c->v4_r1, c->v4_r2,
-                                            c->v4_nh, ext, s);
+                                            c->v4_nh, v, s);
   });
   if (rc != 0) return fail("ecwam_hip_propags2_implsch: no one-kernel build covers the configuration (the strict build of the weights has neither the fast-wave nor the obstruction form)");
   HIPCHK(hipGetLastError());

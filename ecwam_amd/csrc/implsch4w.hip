@@ -1,47 +1,50 @@
 // WDFLUXES (wdfluxes.F90:156-306) and SETICE (setice.F90:67-86) for OUTSTEP0 (outstep0.F90:106-221: the output before the first time step and
 // after a restart).  WDFLUXES is the flux-only mode of k_implsch4 (implsch_v4.h, PART = 3: the source terms evaluated once, nothing advanced)
-// on the common builds (flag sets A and B) and the alternate ones (IPHYS = 0, ISNONLIN = 1 on flag set A), single and double precision (24 directions: single only), with
-// the points per wavefront of implsch4.hip / implsch4x.hip.  A translation unit of its own: the builds of the time step are not recompiled
+// on the common builds (flag sets A and B) and the alternate ones (IPHYS = 0, ISNONLIN = 1 on flag set A), single and double precision (24 directions: single only), at
+// the shapes of implsch_v4_shapes.h.  A translation unit of its own: the builds of the time step are not recompiled
 // with it, nor it with them.
 #include "implsch_v4_launch.h"
 #include "launch.h"
 
-// sel: 0 flag set A, 1 flag set B (EXT), 2 IPHYS 0, 3 ISNONLIN 1.  Returns 0 when launched, -1 when no instantiation covers the configuration.
+// 24 directions: single precision only.  The double precision build (four points per wavefront) gave a wrong PHIWA and Stokes drift on the
+// device while every other instantiation is right; the cause is not found (DESIGN.md section 1 says what is known and what is not): not
+// shipped, ecwam_hip_wdfluxes refuses the configuration (wdfluxes_built).
+// (A developer looking for the cause adds the plain -DECWAM_HIP_WDF_DP24=1 to the flags of this unit.)
+#ifndef ECWAM_HIP_WDF_DP24
+#define ECWAM_HIP_WDF_DP24 0
+#endif
+template <typename T, typename S>
+constexpr bool v4_wdf_built = sizeof(T) == 4 || S::NANG != 24 || ECWAM_HIP_WDF_DP24;
+
+// v: A, B (EXT), iphys0 (JAN) or isnonlin1 (ENHMC).  Returns 0 when launched, -1 when no instantiation covers the configuration.
 template <typename T>
 int launch_wdfluxes(const void* tab, int kijs, int kijl, const void* fl1, const void* wvprpt, const void* ff, void* intf, int* mij, void* xllws,
-                    void* fin, double* w2n, int NANG, int NFRE, int r1, int r2, int nh, int sel, hipStream_t s) {
+                    void* fin, double* w2n, int NANG, int NFRE, int r1, int r2, int nh, Implsch4Variant v, hipStream_t s) {
   if (kijl - kijs <= 0) return 0;
-  if (NFRE != V4_NFRE || sel < 0 || sel > 3) return -1;
-  constexpr bool SP = sizeof(T) == 4;
-#define V4_ARGS tab, kijs, kijl, fl1, wvprpt, ff, intf, mij, xllws, fin, w2n, s
-#define V4_WDF(NANG_, PP_, R1_, R2_, NH_)                                                     \
-  switch (sel) {                                                                              \
-    case 0: return launch4_wdf<T, NANG_, PP_, R1_, R2_, NH_, false>(V4_ARGS);                 \
-    case 1: return launch4_wdf<T, NANG_, PP_, R1_, R2_, NH_, true>(V4_ARGS);                  \
-    case 2: return launch4_wdf<T, NANG_, PP_, R1_, R2_, NH_, false, true, false>(V4_ARGS);    \
-    default: return launch4_wdf<T, NANG_, PP_, R1_, R2_, NH_, false, false, true>(V4_ARGS);   \
-  }
-  if (NANG == 48 && r1 == 1 && r2 == 4 && nh == 11) V4_WDF(48, 2, 1, 4, 11)
-  if (NANG == 36 && r1 == 1 && r2 == 3 && nh == 8) V4_WDF(36, 3, 1, 3, 8)
-  // 24 directions: single precision only.  The double precision build (four points per wavefront) gave a wrong PHIWA and Stokes drift on the
-  // device while every other instantiation is right; the cause is not found (DESIGN.md section 1 says what is known and what is not): not
-  // shipped, ecwam_hip_wdfluxes refuses the configuration.
-  // (A developer looking for the cause adds the plain -DECWAM_HIP_WDF_DP24=1 to the flags of this unit and of capi.hip.)
-#ifdef ECWAM_HIP_WDF_DP24
-  constexpr bool DP24 = true;
-#else
-  constexpr bool DP24 = false;
-#endif
-  if constexpr (SP || DP24) {
-    if (NANG == 24 && r1 == 0 && r2 == 2 && nh == 5) V4_WDF(24, (SP ? 5 : 4), 0, 2, 5)
-  }
-  if (NANG == 12 && r1 == 0 && r2 == 1 && nh == 3) V4_WDF(12, (SP ? 10 : 5), 0, 1, 3)
-#undef V4_WDF
+  if (NFRE != V4_NFRE) return -1;
+  // (the kernel's pointer types are those of the time step; this mode stores through neither fl1 nor ff)
+#define V4_ARGS tab, kijs, kijl, const_cast<void*>(fl1), wvprpt, const_cast<void*>(ff), intf, mij, xllws, fin, w2n, nullptr, 0, nullptr, V4Adv<T>{}, s
+  return v4_for_shape(NANG, r1, r2, nh, [&](auto sh) {
+    using S = decltype(sh);
+    if constexpr (v4_wdf_built<T, S>) {
+      switch (v) {
+        case Implsch4Variant::A: return launch4<T, S, false, false, false, false, V4_WDF>(V4_ARGS);
+        case Implsch4Variant::B: return launch4<T, S, true, false, false, false, V4_WDF>(V4_ARGS);
+        case Implsch4Variant::iphys0: return launch4<T, S, false, true, false, false, V4_WDF>(V4_ARGS);
+        case Implsch4Variant::isnonlin1: return launch4<T, S, false, false, true, false, V4_WDF>(V4_ARGS);
+        default: break;
+      }
+    }
+    return -1;
+  });
 #undef V4_ARGS
-  return -1;
 }
-template int launch_wdfluxes<float>(const void*, int, int, const void*, const void*, const void*, void*, int*, void*, void*, double*, int, int, int, int, int, int, hipStream_t);
-template int launch_wdfluxes<double>(const void*, int, int, const void*, const void*, const void*, void*, int*, void*, void*, double*, int, int, int, int, int, int, hipStream_t);
+template int launch_wdfluxes<float>(const void*, int, int, const void*, const void*, const void*, void*, int*, void*, void*, double*, int, int, int, int, int, Implsch4Variant, hipStream_t);
+template int launch_wdfluxes<double>(const void*, int, int, const void*, const void*, const void*, void*, int*, void*, void*, double*, int, int, int, int, int, Implsch4Variant, hipStream_t);
+// whether WDFLUXES is built at NANG directions in the precision of real_bytes
+bool wdfluxes_built(int NANG, int real_bytes) {
+  return v4_for_nang(NANG, [&](auto sh) { return int(real_bytes == 4 ? v4_wdf_built<float, decltype(sh)> : v4_wdf_built<double, decltype(sh)>); }) == 1;
+}
 
 // SETICE, element-wise: a thread owns the 16 bytes (direction K, frequencies M .. M + VEC - 1) of one sea point.  Where CICOVER > CITHRSH the
 // spectrum becomes MAX(EPSMIN, 1 - CICOVER) FLMIN MAX(0, COS(TH(K) - WDWAVE))**2 (the reference's F * 0 + that: the same value); elsewhere it

@@ -46,20 +46,28 @@ template <typename T> void launch_pack(const void* fl, const int* idx, int n, in
 template <typename T> void launch_proenv_pack(int n, int NFRE, const void* wvprpt, const void* om, const void* depth, const void* u, const void* v, void* buf, hipStream_t s);
 template <typename T> void launch_proenv_unpack(int nrows, int NFRE, const void* buf, const void* land, void* wn, void* cg, void* om, void* dep, void* u, void* v, hipStream_t s);
 
-// ---- implsch4.hip, implsch4x.hip, implsch4r.hip, implsch4a.hip, implsch4w.hip: 0 = launched, -1 = no instantiation covers the configuration ------------
-// sel: EXT (flag set B) for launch_implsch4, the variant (1 = IPHYS 0, 2 = ISNONLIN 1) for launch_implsch4x, JAN (IPHYS 0) for launch_implsch4r
+// ---- implsch4.hip, implsch4x.hip, implsch4r.hip, implsch4a.hip, implsch4w.hip: the launchers of k_implsch4 (implsch_v4.h) ------------------------------
+// The kernel is built at the spectral shapes of implsch_v4_shapes.h, in the variants below; one translation unit per group of variants (they
+// compile side by side).  A context runs ONE variant, computed from its parameters in one place (capi.hip: implsch4_variant); every launcher
+// takes it and returns 0 = launched, -1 = this unit has no build for the variant, the shape (NANG, r1, r2, nh) or the precision.
+//   A, B                flag set A (LLGCBZ0 = F, LLNORMAGAM = F), flag set B (either or both T); IPHYS 1, ISNONLIN 0: implsch4.hip, implsch4a.hip, implsch4w.hip
+//   iphys0, isnonlin1   IPHYS 0, ISNONLIN 1, each on flag set A: implsch4x.hip, implsch4w.hip
+//   rare, rare_iphys0   every other switch, decided at run time inside the build, with IPHYS 1, with IPHYS 0: implsch4r.hip
+enum class Implsch4Variant { A, B, iphys0, isnonlin1, rare, rare_iphys0 };
 template <typename T> int launch_implsch4(const void* tab, int kijs, int kijl, void* fl1, const void* wvprpt, void* ff, void* intf, int* mij, void* xllws, void* fin, double* w2n,
-        void* gfast, int gk, void* wi, int NANG, int NFRE, int r1, int r2, int nh, int sel, hipStream_t s);
+        void* gfast, int gk, void* wi, int NANG, int NFRE, int r1, int r2, int nh, Implsch4Variant v, hipStream_t s);
 template <typename T> int launch_implsch4x(const void* tab, int kijs, int kijl, void* fl1, const void* wvprpt, void* ff, void* intf, int* mij, void* xllws, void* fin, double* w2n,
-        void* gfast, int gk, void* wi, int NANG, int NFRE, int r1, int r2, int nh, int sel, hipStream_t s);
+        void* gfast, int gk, void* wi, int NANG, int NFRE, int r1, int r2, int nh, Implsch4Variant v, hipStream_t s);
 template <typename T> int launch_implsch4r(const void* tab, int kijs, int kijl, void* fl1, const void* wvprpt, void* ff, void* intf, int* mij, void* xllws, void* fin, double* w2n,
-        void* gfast, int gk, void* wi, int NANG, int NFRE, int r1, int r2, int nh, int sel, hipStream_t s);
+        void* gfast, int gk, void* wi, int NANG, int NFRE, int r1, int r2, int nh, Implsch4Variant v, hipStream_t s);
+// the one-kernel step; the forms built for a direction count (bit 0 the plain step, bit 1 fast-wave sub-steps, bit 2 sub-grid obstructions)
 template <typename T> int launch_implsch4_adv(const void* tab, int kijs, int kijl, void* fl_out, const void* wvprpt, void* ff, void* intf, int* mij, void* xllws, void* fin, double* w2n,
-        const Implsch4AdvArgs* a, int NANG, int NFRE, int r1, int r2, int nh, int ext, hipStream_t s);
+        const Implsch4AdvArgs* a, int NANG, int NFRE, int r1, int r2, int nh, Implsch4Variant v, hipStream_t s);
 int implsch4_adv_forms(int NANG, int real_bytes);
-// implsch4w.hip: WDFLUXES (sel: 0 flag set A, 1 flag set B, 2 IPHYS 0, 3 ISNONLIN 1) and SETICE; 0 = launched, -1 = not covered
+// WDFLUXES, whether it is built for a direction count, and SETICE (0 = launched, -1 = not covered)
 template <typename T> int launch_wdfluxes(const void* tab, int kijs, int kijl, const void* fl1, const void* wvprpt, const void* ff, void* intf, int* mij, void* xllws, void* fin,
-        double* w2n, int NANG, int NFRE, int r1, int r2, int nh, int sel, hipStream_t s);
+        double* w2n, int NANG, int NFRE, int r1, int r2, int nh, Implsch4Variant v, hipStream_t s);
+bool wdfluxes_built(int NANG, int real_bytes);
 template <typename T> int launch_setice(const void* tab, int kijs, int kijl, void* fl1, const void* ff, int NANG, int NFRE, hipStream_t s);
 int implsch4_fin_row();
 
