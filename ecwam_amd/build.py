@@ -43,6 +43,9 @@ VARIANTS = {"": FAST_DIV, "exactdiv": ["-DECWAM_HIP_STRICT=0"], "strict1": ["-DE
             # the on-the-fly CTU weights (k_propags2_otf and the advecting load of k_implsch4) in ctuw.F90's order of operations, contraction off:
             # bit-identical to the stored-weight scheme (csrc/ctu.h; the product hoists the factors and fuses the multiply-adds)
             "ctustrict": FAST_DIV,
+            # SINPUT's leading rows without growth through the row loop like every other row (implsch_v4.h::v4_sinput): bit-identical to the
+            # product, which takes them out in front of the loop (tests/test_gpu_sinput_lead.py), and the other side of an A/B in one tree
+            "nolead": FAST_DIV + ["-DV4_SINPUT_LEAD=0"],
             # the one-kernel builds at -O1 (with every double precision direction count enabled in implsch4a.hip this was the proof that their -O3
             # failures are code generation: profiles/r06_fused_step_experiments.txt)
             "advO1": FAST_DIV + ["-O1"]}

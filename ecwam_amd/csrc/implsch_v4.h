@@ -42,6 +42,11 @@
 #else
 #define V4_CHK(c) do { } while (0)
 #endif
+// SINPUT's leading rows without growth taken out of its row loop (single precision, v4_sinput); 0 = the build variant "nolead", every row
+// through the row loop: the bit-identity partner of tests/test_gpu_sinput_lead.py and the other side of an A/B
+#ifndef V4_SINPUT_LEAD
+#define V4_SINPUT_LEAD 1
+#endif
 #define V4_NSTG 4
 // frequencies per lane: lane j of a point owns M = q G + j + 1, q = 0 .. NS - 1 (36 directions: 2, 24: 3, 12: 6; 48 directions: 2 with the
 // second one only on the lanes j < NFRE - G = 12 -- the other lanes repeat frequency NFRE: the same stores, a weight of zero in the sums)
@@ -767,19 +772,131 @@ __device__ void v4_sinput(const DevTab<T>& tb, const V4Ctx<T, NANG, PP>& L, T UF
 #pragma unroll
   for (int s = 0; s < NS; s++) { rX[s] = T(0); rY[s] = T(0); }
   const T* tF = L.tile + L.own;
+  // Single precision: the leading rows in which no direction of any point of the wave grows.  Waves that outrun the wind do not grow
+  // (COSLP > 0.01 and ZCN + UCNZALPD / COSLP < 0 fails in every direction), so at the low-frequency end there is a run of rows with
+  // GAM0 = 0 on every lane and in both gust states.  While XSTRESS = YSTRESS = +0 the chain of a row (sheltered stress, its direction,
+  // U*, COSLP and its reciprocals) does not depend on the row: it is evaluated once, with the expressions of the row loop below.  Then
+  // 1. the length m0 of the run (wave-uniform, 0 .. NFRE): per row U*/c, the two ZLOG per gust state and ONE ballot over "some lane
+  //    grows"; the first row with a lane that grows ends it;
+  // 2. what a row of the run owes, i.e. what does not vanish: zero row integrals, and in the second call the damping DSTAB -> FLP, the
+  //    coefficient store, APL and a zero row total;
+  // 3. the row loop below starts at m0 and runs every row from there on as it always did, with XSTRESS = YSTRESS = +0 at its first row
+  //    as ever -- later rows without growth included.  (m0 is rounded down to an even row, and to NFRE - 2 at most: the loop is unrolled
+  //    by two, and a loop with cross-lane operations is unrolled only where that needs no remainder.)
+  // The chain, COSLP, the ZLOG test and DSTAB are written TWICE in this function, here and in the row loop: an edit of one is an edit of
+  // the other, and only tests/test_gpu_sinput_lead.py (product against "nolead") holds them together.
+  // The same bits as the row loop gives for such a row, for finite NON-NEGATIVE spectra (the FLMIN floor of the spectrum; with F < 0 or
+  // F = -0 the row loop's SLP = (+0) F = -0 and its FL F - SLP could differ from FL F - (+0) here in the sign of a zero): every quantity left out is a sum or a product of zeros --
+  // SLP = GAM0 F, the five row totals, the XLLWS bits, the windsea integrands -- added to an accumulator that starts at +0 (XSTRESS,
+  // YSTRESS, wse, the sums of post_stress, apl); in round-to-nearest x + (+-0) = x and (+0) + (+-0) = +0, so the stress stays +0 and
+  // the next row's chain has this row's inputs.  The ballot is over all 64 lanes: shadows and extras replicate real lanes of the
+  // wave, a short last wave replicates its last point.  Every shape (36 / 48 / 24 / 12 directions) and every caller (step, split,
+  // WDFLUXES with UNI, the ADV builds) runs this code.  -DV4_SINPUT_LEAD=0 (build variant "nolead") is the bit-identity partner
+  // (tests/test_gpu_sinput_lead.py); measurements: DESIGN.md section 3, profiles/r08_sinput_lead_isa.txt.
+  constexpr bool LEAD = (V4_SINPUT_LEAD != 0) && sizeof(T) == 4;
+  int m0 = 0;
+  if constexpr (LEAD) {
+    const V2<T> vTPX = vTAUX - ABS_TAUWSHELTER * vXS, vTPY = vTAUY - ABS_TAUWSHELTER * vYS;
+    const V2<T> vh2 = vTPX * vTPX + vTPY * vTPY;
+    const T TINY = sizeof(T) == 4 ? T(1e-36) : T(1e-300);
+    V2<T> vrh = {fs_rsq<8>(m_max(vh2.x, TINY)), (NGST == 2) ? fs_rsq<8>(m_max(vh2.y, TINY)) : T(0)};
+    if (NGST == 1) vrh.y = vrh.x;
+    const V2<T> vh = vh2 * vrh, vCOSU = vTPY * vrh, vSINU = vTPX * vrh;
+    V2<T> vUSTP0 = V2<T>{fs_sqrt<8>(vh.x), (NGST == 2) ? fs_sqrt<8>(vh.y) : T(0)};
+    if (NGST == 1) vUSTP0.y = vUSTP0.x;
+    V2<T> rcl[NGST], ds2[NGST];      // 1 / COSLP of the lane's pair; TEMP2 + (FU + FUD COSLP) USTP of DSTAB2
+    bool c0[NGST], c1[NGST];
+#pragma unroll
+    for (int ig = 0; ig < NGST; ig++) {
+      const T COSU = ig ? vCOSU.y : vCOSU.x, SINU = ig ? vSINU.y : vSINU.x;
+      const T USTPg = ig ? vUSTP0.y : vUSTP0.x;
+      const V2<T> coslp = L.costh * COSU + L.sinth * SINU;
+      c0[ig] = coslp.x > T(0.01); c1[ig] = coslp.y > T(0.01);
+      rcl[ig] = V2<T>{fs_rcp<4>(coslp.x), fs_rcp<4>(coslp.y)};
+      ds2[ig] = LLSNEG ? TEMP2 + (FU + FUD * coslp) * USTPg : z2;
+    }
+    // 1. the length of the run: nothing but the test, the next row's CINV and LOG(WAVNUM Z0M) read ahead of it
+    {
+      T ci_n = L.fac4[Q4_CINV], zcn_l = L.zcn[0];
+#pragma unroll 1
+      for (; m0 < NFRE; m0++) {
+        const T cinv_m = ci_n, ZCN = zcn_l;
+        const int mn = m0 + 1 < NFRE ? m0 + 1 : m0;
+        ci_n = L.fac4[mn * 4 + Q4_CINV];
+        zcn_l = L.zcn[mn];
+        const V2<T> vUCN = vUSTP0 * cinv_m;
+        const V2<T> vden = vUCN + ZALP;
+        const V2<T> vUZ = XKAPPA * V2<T>{fs_rcp<8>(vden.x), (NGST == 2) ? fs_rcp<8>(vden.y) : T(0)};
+        bool grows = false;
+#pragma unroll
+        for (int ig = 0; ig < NGST; ig++) {
+          const T UCNZALPD = ig ? vUZ.y : vUZ.x;
+          const T Z0 = ZCN + UCNZALPD * rcl[ig].x, Z1 = ZCN + UCNZALPD * rcl[ig].y;
+          const bool n0 = c0[ig] && (Z0 < T(0)), n1 = c1[ig] && (Z1 < T(0));
+          grows = grows || n0 || n1;
+        }
+        if (__builtin_amdgcn_ballot_w64(grows) != 0ull) break;
+      }
+    }
+    // (the row loop takes its rows in pairs: an odd run gives its last row back to it, and a run of all NFRE rows its last two, so that the
+    // one-row-ahead operands below are read inside the tables)
+    static_assert(NFRE % 2 == 0, "the row loop takes its rows in pairs");
+    m0 = m0 < NFRE ? (m0 & ~1) : NFRE - 2;
+    // 2. what the rows of the run owe
+    if constexpr (G == 18) {
+      for (int m = 0; m < m0; m++) *reinterpret_cast<V2<T>*>(sXY + 2 * m) = z2;      // (the other shapes: rX / rY are zero already)
+    }
+    if constexpr (LLSNEG) {
+      if (m0 > 0) {
+        // C5, T1 and RHOWG_DFIM of row l in lane l, handed out by v_readlane: a scalar load per row would be waited for where it is issued
+        const int lr = L.lane < NFRE ? L.lane : NFRE - 1;
+        const T k2 = tb.SINROW[lr][2], k3 = tb.SINROW[lr][3], k4 = tb.SINROW[lr][4];
+        V2<T> f_l = *reinterpret_cast<const V2<T>*>(tF);
+        T wn_l = L.fac4[Q4_CINV + 1];
+#pragma unroll 1
+        for (int m = 0; m < m0; m++) {
+          const V2<T> f = f_l;
+          const T wavnum_m = wn_l;
+          const int mn = m + 1 < NFRE ? m + 1 : m;
+          f_l = *reinterpret_cast<const V2<T>*>(tF + mn * RS);
+          wn_l = L.fac4[mn * 4 + Q4_CINV + 1];
+          const T row2 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(k2), m));
+          const T row3 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(k3), m));
+          const T row4 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(k4), m));
+          const T DSTAB1 = (row2 * AIRD_PVISC) * wavnum_m;
+          const T TEMP1 = row3 * RAORW;
+          V2<T> FLP[NGST];
+#pragma unroll
+          for (int ig = 0; ig < NGST; ig++) {
+            const V2<T> DSTAB2 = TEMP1 * ds2[ig];
+            const V2<T> dstab = DSTAB1 + PTURB * DSTAB2;
+            FLP[ig] = z2 + dstab;      // GAM0 = +0: the addition stays (a DSTAB of -0 gives +0 as in the row loop)
+          }
+          V2<T> fl = FLP[0];
+          if (NGST == 2) fl = fl + FLP[NGST - 1];
+          fl = AVG * fl;
+          apl = apl + (fl * f - z2) * row4;
+          *reinterpret_cast<V2<T>*>(gfl + (size_t)m * NANG) = fl;
+          gsp[m] = T(0);
+        }
+      }
+    }
+  }
   // operands of the next row are read one row ahead (the row itself, CINV / WAVNUM, LOG(WAVNUM Z0M))
-  V2<T> f_n = *reinterpret_cast<const V2<T>*>(tF);
-  V2<T> cw_n = *reinterpret_cast<const V2<T>*>(L.fac4 + Q4_CINV);
-  T zcn_n = L.zcn[0];
+  // (the row loop starts at m0, which is even: the unroll by two needs no remainder -- a loop with cross-lane operations is given none)
+  const int mp = LEAD ? 2 * (int)((unsigned)m0 >> 1) : 0;
+  V2<T> f_n = *reinterpret_cast<const V2<T>*>(tF + mp * RS);
+  V2<T> cw_n = *reinterpret_cast<const V2<T>*>(L.fac4 + mp * 4 + Q4_CINV);
+  T zcn_n = L.zcn[mp];
   // single precision: the row's record of module constants one row ahead as well (its scalar load would otherwise be waited for where it is issued)
   constexpr bool RPF = sizeof(T) == 4;
   T rw_n[6];
   if constexpr (RPF) {
 #pragma unroll
-    for (int i = 0; i < 6; i++) rw_n[i] = tb.SINROW[0][i];
+    for (int i = 0; i < 6; i++) rw_n[i] = tb.SINROW[mp][i];
   }
 #pragma unroll 2
-  for (int m = 0; m < NFRE; m++) {
+  for (int m = mp; m < NFRE; m++) {
     const V2<T> f = f_n, cw = cw_n;
     const T ZCN = zcn_n, cinv_m = cw.x;
     T rw[6];
@@ -807,6 +924,7 @@ __device__ void v4_sinput(const DevTab<T>& tb, const V4Ctx<T, NANG, PP>& L, T UF
     const T TEMP1 = LLSNEG ? row[3] * RAORW : T(0);
     V2<T> SLP[2], FLP[2];
     bool xl0 = false, xl1 = false;
+    // (the chain, COSLP, the ZLOG test and DSTAB below have a copy in front of the loop, single precision's leading run: edit both)
     const V2<T> vTPX = vTAUX - ABS_TAUWSHELTER * vXS, vTPY = vTAUY - ABS_TAUWSHELTER * vYS;
     const V2<T> vh2 = vTPX * vTPX + vTPY * vTPY;
     // |TAUP| = h2 / SQRT(h2) with the root of MAX(h2, tiny): a vanishing stress gives h = 0 exactly and a finite direction (0, 0) --
@@ -831,8 +949,10 @@ __device__ void v4_sinput(const DevTab<T>& tb, const V4Ctx<T, NANG, PP>& L, T UF
         const bool c0 = coslp.x > T(0.01), c1 = coslp.y > T(0.01);
         const T Z0 = ZCN + UCNZALPD * fs_rcp<4>(coslp.x), Z1 = ZCN + UCNZALPD * fs_rcp<4>(coslp.y);
         const bool n0 = c0 && (Z0 < T(0)), n1 = c1 && (Z1 < T(0));
-        // single precision: no test for "no lane grows" -- a uniform branch here costs more than the two v_exp_f32 it would skip;
-        // the double-precision exponentials are long instruction sequences worth skipping
+        // single precision: no test for "no lane grows" per row and gust state HERE -- it would guard only the two v_exp_f32, and a
+        // uniform branch costs more than they do; the rows it is worth testing for, the leading run in which no lane grows in either
+        // gust state, are taken out in front of this loop by one ballot per row, which skips the chain and the all-reduces with them.
+        // The double-precision exponentials are long instruction sequences worth skipping
         if (sizeof(T) == 4 || __builtin_amdgcn_ballot_w64(n0 || n1) != 0ull) {
           const V2<T> ZL = {Z0, Z1};
           const V2<T> Z2X = ZL * ZL * (coslp * UCN);
