@@ -364,6 +364,104 @@ class HipContext:
         self._chk(self.lib.ecwam_hip_getspec_tail(self._h, kijs, kijl, *self._start_rows("GETSPEC", kijs, kijl, fl1, ff),
                                                   int(self.NR if nfre_red is None else nfre_red), _stream_ptr()))
 
+    # -- the forcing and coupling seam (include/ecwam_hip_forcing.h; csrc/forcing.hip): what WAVEMDL runs immediately before and after WAMODEL
+    def set_forcing_map(self, ixy_in=None, ncell_in: int = 0, ixy_out=None, ncell_out: int = 0) -> None:
+        """The maps row -> cell (0-based, host integers of one length): ixy_in into the planes of fieldg (ncell_in cells each), ixy_out into the
+        outbound grid (ncell_out cells, no cell twice).  None removes a map.  The library validates and uploads them."""
+        a = [None if m is None else np.ascontiguousarray(m, dtype=np.int32).reshape(-1) for m in (ixy_in, ixy_out)]
+        if a[0] is not None and a[1] is not None and a[0].size != a[1].size:
+            raise ValueError("set_forcing_map: the two maps differ in length")
+        npts = next((m.size for m in a if m is not None), 0)
+        ptr = [None if m is None else m.ctypes.data_as(C.c_void_p) for m in a]
+        self._chk(self.lib.ecwam_hip_set_forcing_map(self._h, npts, ptr[0], int(ncell_in), ptr[1], int(ncell_out)))
+        self._fmap = (npts, int(ncell_in) if a[0] is not None else 0, int(ncell_out) if a[1] is not None else 0)
+
+    def _seam(self, who, kijs, kijl, *rows):
+        if not (0 <= kijs <= kijl <= min(a.shape[0] for a in rows)):
+            raise ValueError(f"{who}: KIJS/KIJL outside the operands")
+
+    def _fieldg(self, fieldg):
+        ncell = getattr(self, "_fmap", (0, 0, 0))[1]
+        return None if fieldg is None else self._real(fieldg, (len(_lib.FG_PLANES), ncell), "FIELDG")
+
+    def _nemo(self, nemo, kijl):
+        """float64 [4][>= kijl] -> the planes of exactly kijl points the library takes (kept alive by the caller of this method)"""
+        if nemo is None:
+            return None
+        if not (nemo.is_cuda and nemo.dtype == torch.float64 and nemo.dim() == 2 and nemo.shape[0] == 4 and nemo.shape[1] >= kijl):
+            raise ValueError("NEMO: expected a float64 cuda tensor [4][>= KIJL]")
+        return nemo[:, :kijl].contiguous()
+
+    def getwnd(self, kijs, kijl, fieldg, ff, ucur=None, vcur=None, nemo=None, icode_wnd: int | None = None, llwswave: bool = False, llwdwave: bool = False,
+               lcorrel: bool = False, rwfac: float = 1.0, iparamci: int = 31, lwcou: bool | None = None, lwnemocoucic: bool = False,
+               lwnemocoucit: bool = False, lnemoicerest: bool = False, liceth: bool = False, swamp: bool = False, swampcith: float = 0.0,
+               zmiss: float = -999.0):
+        """GETWND per chunk (getwnd.F90:211-229) on rows [kijs, kijl) of ff: WAMWND, then MICEP, from the planes fieldg [13][ncell_in] (lib.FG_PLANES)
+        through the inbound map.  icode_wnd defaults to ICODE and lwcou to LWCOU of the parameters; lcorrel is LCORREL of wamwnd.F90:127-133."""
+        c = self.t.cfg
+        o = _lib.ForcingOpts(int(c.icode if icode_wnd is None else icode_wnd), int(llwswave), int(llwdwave), int(lcorrel), float(rwfac), int(iparamci),
+                             int(c.lwcou if lwcou is None else lwcou), int(lwnemocoucic), int(lwnemocoucit), int(lnemoicerest), int(liceth), int(swamp),
+                             float(swampcith), float(zmiss))
+        self._seam("GETWND", kijs, kijl, ff, *[a for a in (ucur, vcur) if a is not None])
+        opt = lambda a, name: None if a is None else self._real(a, (a.shape[0],), name)
+        pn = self._nemo(nemo, kijl)
+        self._chk(self.lib.ecwam_hip_getwnd(self._h, kijs, kijl, self._fieldg(fieldg), opt(ucur, "UCUR"), opt(vcur, "VCUR"), None if pn is None else pn.data_ptr(),
+                                            self._real(ff, (ff.shape[0], NFF), "FF"), C.byref(o), _stream_ptr()))
+
+    def cdustarz0(self, kijs, kijl, ff):
+        """CDUSTARZ0 with ZREF = XNLEV (getfrstwnd.F90:125-126): UFRIC and Z0M of ff from its WSWAVE on rows [kijs, kijl)."""
+        self._seam("CDUSTARZ0", kijs, kijl, ff)
+        self._chk(self.lib.ecwam_hip_cdustarz0(self._h, kijs, kijl, self._real(ff, (ff.shape[0], NFF), "FF"), _stream_ptr()))
+
+    def wamadswstar(self, kijs, kijl, fieldg, ff):
+        """WAMADSWSTAR (wamadswstar.F90:60-69): AIRD, WSTAR, USTRA, VSTRA of ff from fieldg on rows [kijs, kijl)."""
+        self._seam("WAMADSWSTAR", kijs, kijl, ff)
+        self._chk(self.lib.ecwam_hip_wamadswstar(self._h, kijs, kijl, self._fieldg(fieldg), self._real(ff, (ff.shape[0], NFF), "FF"), _stream_ptr()))
+
+    def getcurr(self, kijs, kijl, mode, ucur, vcur, fieldg=None, nemo=None, changed=None):
+        """The point-wise part of GETCURR on rows [kijs, kijl) of ucur / vcur: mode 0 WAMCUR from fieldg, 1 the NEMO currents (nemo float64
+        [4][>= kijl], planes 2 and 3) where LKFR of fieldg <= 0, 2 zero.  changed: an int32 cuda tensor of one element that becomes 1 if a value
+        changed (KUPDATE); the call never clears it."""
+        self._seam("GETCURR", kijs, kijl, ucur, vcur)
+        pn = self._nemo(nemo, kijl)
+        self._chk(self.lib.ecwam_hip_getcurr(self._h, kijs, kijl, int(mode), self._fieldg(fieldg), None if pn is None else pn.data_ptr(),
+                                             self._real(ucur, (ucur.shape[0],), "UCUR"), self._real(vcur, (vcur.shape[0],), "VCUR"),
+                                             None if changed is None else self._int(changed, (1,), "CHANGED"), _stream_ptr()))
+
+    def wvblock(self, kijs, kijl, wvblock, ff=None, intf=None, lwcou2w: bool = False, lwcouhmf: bool = False, lwstokes: bool = False, lwflux: bool = False,
+                prchar: float = 0.0185, flags: int | None = None):
+        """The WVBLOCK fill of wavemdl.F90:757-802 on rows [kijs, kijl) of wvblock [NWVFIELDS][ld]: OUTBETA's BETAM (and BETAHQ) with lwcou2w,
+        otherwise prchar; then the fields of intf the switches name, then zeros.  flags (the lib.WVB_* bits) overrides the four switches."""
+        if flags is None:
+            flags = (_lib.WVB_LWCOU2W if lwcou2w else 0) | (_lib.WVB_LWCOUHMF if lwcouhmf else 0) | (_lib.WVB_LWSTOKES if lwstokes else 0) | \
+                (_lib.WVB_LWFLUX if lwflux else 0)
+        if wvblock.dim() != 2:
+            raise ValueError("WVBLOCK: expected [NWVFIELDS][ld]")
+        nwv, ld = wvblock.shape
+        if not (0 <= kijs <= kijl <= ld):
+            raise ValueError("WVBLOCK: KIJS/KIJL outside the operands")
+        self._seam("WVBLOCK", kijs, kijl, *[a for a in (ff, intf) if a is not None])
+        self._chk(self.lib.ecwam_hip_wvblock(self._h, kijs, kijl, None if ff is None else self._real(ff, (ff.shape[0], NFF), "FF"),
+                                             None if intf is None else self._real(intf, (intf.shape[0], NINTF), "INTF"), int(flags), nwv, float(prchar),
+                                             self._real(wvblock, (nwv, ld), "WVBLOCK"), ld, _stream_ptr()))
+
+    def fldtoifs(self, kijs, kijl, wvblock, grid, defval=None):
+        """MPFLDTOIFS on one task: rows [kijs, kijl) of wvblock [NWVFIELDS][ld] into grid [NWVFIELDS][ncell_out] through the outbound map; with
+        defval (NWVFIELDS host numbers) the whole grid is set to the defaults first (LLINIT_GRID)."""
+        if wvblock.dim() != 2:
+            raise ValueError("FLDTOIFS: expected WVBLOCK [NWVFIELDS][ld]")
+        nwv, ld = wvblock.shape
+        if not (0 <= kijs <= kijl <= ld):
+            raise ValueError("FLDTOIFS: KIJS/KIJL outside the operands")
+        d = None
+        if defval is not None:
+            d = np.ascontiguousarray(defval, dtype=np.float64).reshape(-1)
+            if d.size != nwv:
+                raise ValueError("FLDTOIFS: one default per field")
+        ncell = getattr(self, "_fmap", (0, 0, 0))[2]
+        self._chk(self.lib.ecwam_hip_fldtoifs(self._h, kijs, kijl, self._real(wvblock, (nwv, ld), "WVBLOCK"), ld, nwv,
+                                              None if d is None else d.ctypes.data_as(C.c_void_p), self._real(grid, (nwv, ncell), "GRID"), _stream_ptr()))
+
     # -- nested grids: BOUINPT / INTSPEC (bouinpt.F90:385-424) and OUTBC (outbc.F90:78-91), the two calls of wamodel.F90:333-343
     def bouinpt(self, kijs, kijl, ijb, ibcl, ibcr, bfw, f1, par1, fl1, par_out=None):
         """The coarse model's boundary spectra into the rows ijb (0-based, distinct) of FL1 that lie in [kijs, kijl): ibcl / ibcr = IBFL / IBFR

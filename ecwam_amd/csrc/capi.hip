@@ -9,6 +9,7 @@
 #include <dlfcn.h>
 #include <rccl/rccl.h>   // types and prototypes only: librccl is loaded with dlopen when a communicator is asked for
 
+#include "../../include/ecwam_hip_forcing.h"
 #include "../../include/ecwam_hip_start.h"
 #include "dev.h"
 #include "implsch_v4_shapes.h"
@@ -91,6 +92,11 @@ struct ecwam_hip_ctx {
   int* ob_desc = nullptr;
   void* ob_work = nullptr;
   size_t ob_work_bytes = 0;
+  // ecwam_hip_set_forcing_map (csrc/forcing.hip): the validated maps row -> cell on the device, [fmap_n] each, and the cells of their grids
+  int* fmap_in = nullptr;
+  int* fmap_out = nullptr;
+  int fmap_n = 0;
+  size_t fmap_ncell_in = 0, fmap_ncell_out = 0;
   const void* obs = nullptr;  // LSUBGRID: device OBS[n_obs][8][NFRE] (ecwam_hip_set_obstructions), read by CTUW / PROPAGS2
   int n_obs = 0;
 };
@@ -522,6 +528,8 @@ int ecwam_hip_destroy(ecwam_hip_ctx* c) {
   if (c->wi) (void)hipFree(c->wi);
   if (c->adv_pt) (void)hipFree(c->adv_pt);
   if (c->adv_dir) (void)hipFree(c->adv_dir);
+  if (c->fmap_in) (void)hipFree(c->fmap_in);
+  if (c->fmap_out) (void)hipFree(c->fmap_out);
   halo_release(c);
   delete c;
   return 0;
@@ -931,6 +939,122 @@ int ecwam_hip_getspec_tail(ecwam_hip_ctx* c, int kijs, int kijl, void* fl1, cons
   return start_done("ecwam_hip_getspec_tail", in_precision(c, [&](auto t) {
     return launch_getspec_tail<decltype(t)>(c->dtab, kijs, kijl, fl1, ff, nfre_red, c->NANG, c->NFRE, (hipStream_t)stream);
   }));
+}
+
+// The forcing and coupling seam (include/ecwam_hip_forcing.h; csrc/forcing.hip).  The checks every call on rows makes, in the order of
+// ecwam_hip_setice; 0 = go on.  Each buffer: the pointer, whether the call touches it when the range is not empty.
+struct SeamBuf { const void* p; bool used; };
+static int seam_checks(ecwam_hip_ctx* c, const std::string& who, int kijs, int kijl, const char* map, std::initializer_list<SeamBuf> bufs) {
+  if (kijl < kijs || kijs < 0) return fail(who + ": bad range");
+  if (map && !(map[0] == 'i' ? c->fmap_in : c->fmap_out)) return fail(who + ": no " + map + " map");
+  if (map && kijl > c->fmap_n) return fail(who + ": bad range");
+  HIPCHK(hipSetDevice(c->device));
+  for (const SeamBuf& b : bufs)
+    if (kijl > kijs && b.used && !b.p) return fail(who + ": null pointer");
+  for (const SeamBuf& b : bufs)
+    if (b.used && ((uintptr_t)b.p % 16) != 0) return fail(who + ": the buffers must be 16-byte aligned");
+  return 0;
+}
+int ecwam_hip_set_forcing_map(ecwam_hip_ctx* c, int npts, const int* ixy_in, int ncell_in, const int* ixy_out, int ncell_out) {
+  if (!c) return fail("null context");
+  if (npts < 0) return fail("ecwam_hip_set_forcing_map: negative count");
+  if ((ixy_in && ncell_in < 1) || (ixy_out && ncell_out < 1)) return fail("ecwam_hip_set_forcing_map: a map needs a grid of at least one cell");
+  for (int i = 0; ixy_in && i < npts; i++)
+    if (ixy_in[i] < 0 || ixy_in[i] >= ncell_in) return fail("ecwam_hip_set_forcing_map: inbound index " + std::to_string(i) + " outside [0, ncell_in)");
+  if (ixy_out) {
+    std::vector<unsigned char> seen((size_t)ncell_out, 0);
+    for (int i = 0; i < npts; i++) {
+      if (ixy_out[i] < 0 || ixy_out[i] >= ncell_out) return fail("ecwam_hip_set_forcing_map: outbound index " + std::to_string(i) + " outside [0, ncell_out)");
+      if (seen[ixy_out[i]]) return fail("ecwam_hip_set_forcing_map: outbound index " + std::to_string(i) + " is a duplicate (two rows would write one cell)");
+      seen[ixy_out[i]] = 1;
+    }
+  }
+  HIPCHK(hipSetDevice(c->device));
+  // a copy another stream may still read is not freed under it
+  HIPCHK(hipDeviceSynchronize());
+  if (c->fmap_in) { (void)hipFree(c->fmap_in); c->fmap_in = nullptr; }
+  if (c->fmap_out) { (void)hipFree(c->fmap_out); c->fmap_out = nullptr; }
+  c->fmap_n = npts; c->fmap_ncell_in = c->fmap_ncell_out = 0;
+  const size_t bytes = (size_t)(npts > 0 ? npts : 1) * sizeof(int);
+  if (ixy_in) {
+    HIPCHK(hipMalloc((void**)&c->fmap_in, bytes));
+    if (npts > 0) HIPCHK(hipMemcpy(c->fmap_in, ixy_in, (size_t)npts * sizeof(int), hipMemcpyHostToDevice));
+    c->fmap_ncell_in = (size_t)ncell_in;
+  }
+  if (ixy_out) {
+    HIPCHK(hipMalloc((void**)&c->fmap_out, bytes));
+    if (npts > 0) HIPCHK(hipMemcpy(c->fmap_out, ixy_out, (size_t)npts * sizeof(int), hipMemcpyHostToDevice));
+    c->fmap_ncell_out = (size_t)ncell_out;
+  }
+  return 0;
+}
+int ecwam_hip_getwnd(ecwam_hip_ctx* c, int kijs, int kijl, const void* fieldg, const void* ucur, const void* vcur, const double* nemo, void* ff,
+                     const ecwam_hip_forcing_opts* o, void* stream) {
+  if (!c) return fail("null context");
+  const std::string who = "ecwam_hip_getwnd";
+  if (!o) return fail(who + ": null options");
+  if (o->icode_wnd < 1 || o->icode_wnd > 3) return fail(who + ": ICODE_WND must be 1, 2 or 3");
+  if (!o->lwnemocoucic && o->iparamci != 31 && o->iparamci != 139) return fail(who + ": IPARAMCI must be 31 or 139 unless LWNEMOCOUCIC");
+  const bool cur = o->lcorrel != 0 && o->icode_wnd == 3, nm = o->lwnemocoucic || o->lwnemocoucit;
+  if (int rc = seam_checks(c, who, kijs, kijl, "inbound", {{fieldg, true}, {ff, true}, {ucur, cur}, {vcur, cur}, {nemo, nm}})) return rc;
+  in_precision(c, [&](auto t) {
+    launch_getwnd<decltype(t)>(c->dtab, kijs, kijl, c->fmap_in, fieldg, c->fmap_ncell_in, ucur, vcur, nemo, ff, *o, (hipStream_t)stream);
+  });
+  return launched();
+}
+int ecwam_hip_cdustarz0(ecwam_hip_ctx* c, int kijs, int kijl, void* ff, void* stream) {
+  if (!c) return fail("null context");
+  if (int rc = seam_checks(c, "ecwam_hip_cdustarz0", kijs, kijl, nullptr, {{ff, true}})) return rc;
+  in_precision(c, [&](auto t) { launch_cdustarz0<decltype(t)>(c->dtab, kijs, kijl, ff, (hipStream_t)stream); });
+  return launched();
+}
+int ecwam_hip_wamadswstar(ecwam_hip_ctx* c, int kijs, int kijl, const void* fieldg, void* ff, void* stream) {
+  if (!c) return fail("null context");
+  if (int rc = seam_checks(c, "ecwam_hip_wamadswstar", kijs, kijl, "inbound", {{fieldg, true}, {ff, true}})) return rc;
+  in_precision(c, [&](auto t) { launch_wamadswstar<decltype(t)>(kijs, kijl, c->fmap_in, fieldg, c->fmap_ncell_in, ff, (hipStream_t)stream); });
+  return launched();
+}
+int ecwam_hip_getcurr(ecwam_hip_ctx* c, int kijs, int kijl, int mode, const void* fieldg, const double* nemo, void* ucur, void* vcur, int* changed,
+                      void* stream) {
+  if (!c) return fail("null context");
+  const std::string who = "ecwam_hip_getcurr";
+  if (mode < 0 || mode > 2) return fail(who + ": mode must be 0 (WAMCUR), 1 (NEMO) or 2 (zero)");
+  if (int rc = seam_checks(c, who, kijs, kijl, mode == 2 ? nullptr : "inbound", {{fieldg, mode != 2}, {nemo, mode == 1}, {ucur, true}, {vcur, true}})) return rc;
+  if (((uintptr_t)changed % sizeof(int)) != 0) return fail(who + ": the buffers must be 16-byte aligned");
+  in_precision(c, [&](auto t) {
+    launch_getcurr<decltype(t)>(kijs, kijl, mode, c->fmap_in, fieldg, c->fmap_ncell_in, nemo, ucur, vcur, changed, (hipStream_t)stream);
+  });
+  return launched();
+}
+int ecwam_hip_wvblock(ecwam_hip_ctx* c, int kijs, int kijl, const void* ff, const void* intf, int flags, int nwvfields, double prchar, void* wvblock, int ld,
+                      void* stream) {
+  if (!c) return fail("null context");
+  const std::string who = "ecwam_hip_wvblock";
+  const int all = ECWAM_HIP_WVB_LWCOU2W | ECWAM_HIP_WVB_LWCOUHMF | ECWAM_HIP_WVB_LWSTOKES | ECWAM_HIP_WVB_LWFLUX;
+  if (flags & ~all) return fail(who + ": unknown flags");
+  if ((flags & ECWAM_HIP_WVB_LWCOUHMF) && !(flags & ECWAM_HIP_WVB_LWCOU2W)) return fail(who + ": LWCOUHMF needs LWCOU2W (without OUTBETA there is no BETAHQ)");
+  const int need = 1 + ((flags & ECWAM_HIP_WVB_LWCOUHMF) ? 1 : 0) + ((flags & ECWAM_HIP_WVB_LWSTOKES) ? 2 : 0) + ((flags & ECWAM_HIP_WVB_LWFLUX) ? 7 : 0);
+  if (nwvfields < need) return fail(who + ": nwvfields is smaller than the switches need (" + std::to_string(need) + ")");
+  if (nwvfields > ECWAM_HIP_MAXWVFIELDS) return fail(who + ": nwvfields above ECWAM_HIP_MAXWVFIELDS");
+  const bool rf = (flags & ECWAM_HIP_WVB_LWCOU2W) != 0, ri = (flags & (ECWAM_HIP_WVB_LWSTOKES | ECWAM_HIP_WVB_LWFLUX)) != 0;
+  if (int rc = seam_checks(c, who, kijs, kijl, nullptr, {{ff, rf}, {intf, ri}, {wvblock, true}})) return rc;
+  if (ld < kijl) return fail(who + ": bad range");
+  in_precision(c, [&](auto t) {
+    launch_wvblock<decltype(t)>(c->dtab, c->p.llgcbz0, kijs, kijl, ff, intf, flags, nwvfields, prchar, wvblock, ld, (hipStream_t)stream);
+  });
+  return launched();
+}
+int ecwam_hip_fldtoifs(ecwam_hip_ctx* c, int kijs, int kijl, const void* wvblock, int ld, int nwvfields, const double* defval, void* grid, void* stream) {
+  if (!c) return fail("null context");
+  const std::string who = "ecwam_hip_fldtoifs";
+  if (nwvfields < 1 || nwvfields > ECWAM_HIP_MAXWVFIELDS) return fail(who + ": nwvfields outside 1 .. ECWAM_HIP_MAXWVFIELDS");
+  if (int rc = seam_checks(c, who, kijs, kijl, "outbound", {{wvblock, true}, {grid, true}})) return rc;
+  if (ld < kijl) return fail(who + ": bad range");
+  if (defval && !grid) return fail(who + ": null pointer");
+  in_precision(c, [&](auto t) {
+    launch_fldtoifs<decltype(t)>(kijs, kijl, c->fmap_out, wvblock, ld, nwvfields, defval, grid, c->fmap_ncell_out, (hipStream_t)stream);
+  });
+  return launched();
 }
 
 // bit 0: the one-kernel step covers the context; bit 1: also with fast-wave sub-steps (gin); bit 2: also with the obstructions of

@@ -8,7 +8,7 @@
 
 #include <hip/hip_runtime.h>
 
-#include "../../include/ecwam_hip.h"
+#include "../../include/ecwam_hip_forcing.h"
 #include "implsch_adv_args.h"
 
 // The grid geometry the advection kernels form the CTU weights from, in the untyped form and the order of the C interface's arguments
@@ -118,6 +118,19 @@ template <typename T> int launch_unsetice(const void* tab, int kijs, int kijl, v
         hipStream_t s);
 template <typename T> int launch_getspec_noise(const void* tab, int kijs, int kijl, void* fl1, int NANG, int NFRE, hipStream_t s);
 template <typename T> int launch_getspec_tail(const void* tab, int kijs, int kijl, void* fl1, const void* ff, int nfre_red, int NANG, int NFRE, hipStream_t s);
+
+// ---- forcing.hip: the forcing and coupling seam (include/ecwam_hip_forcing.h).  map = the validated map of ecwam_hip_set_forcing_map on the device, ncell the
+// cells of a plane of fieldg / grid; nemo = double [4][kijl].  An empty range launches nothing (launch_fldtoifs still sets the defaults). ------------------------
+template <typename T> void launch_getwnd(const void* tab, int kijs, int kijl, const int* map, const void* fieldg, size_t ncell, const void* ucur, const void* vcur,
+        const double* nemo, void* ff, const ecwam_hip_forcing_opts& o, hipStream_t s);
+template <typename T> void launch_cdustarz0(const void* tab, int kijs, int kijl, void* ff, hipStream_t s);
+template <typename T> void launch_wamadswstar(int kijs, int kijl, const int* map, const void* fieldg, size_t ncell, void* ff, hipStream_t s);
+template <typename T> void launch_getcurr(int kijs, int kijl, int mode, const int* map, const void* fieldg, size_t ncell, const double* nemo, void* ucur, void* vcur,
+        int* changed, hipStream_t s);
+template <typename T> void launch_wvblock(const void* tab, int llgcbz0, int kijs, int kijl, const void* ff, const void* intf, int flags, int nwvfields, double prchar,
+        void* wvblock, int ld, hipStream_t s);
+template <typename T> void launch_fldtoifs(int kijs, int kijl, const int* map, const void* wvblock, int ld, int nwvfields, const double* defval, void* grid, size_t ncell,
+        hipStream_t s);
 
 // ---- outblock.hip: OUTBLOCK itself (outblock.F90:159-610) -- the plan of ecwam_hip_set_outblock and the kernel that fills BOUT ---------------------
 // where a BOUT column comes from: the packed buffers of the output calls (in the work space of the context), the caller's per-point arrays, or nothing

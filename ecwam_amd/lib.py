@@ -66,6 +66,21 @@ EXPORTS = ["ecwam_hip_last_error", "ecwam_hip_abi_version", "ecwam_hip_selftest"
 # include/ecwam_hip_start.h: the start spectra, added to ABI 6 in a header and a list of their own (EXPORTS is the list of include/ecwam_hip.h)
 EXPORTS_START = ["ecwam_hip_mstart", "ecwam_hip_unsetice", "ecwam_hip_getspec_noise", "ecwam_hip_getspec_tail"]
 
+# include/ecwam_hip_forcing.h: the forcing and coupling seam around WAMODEL, added to ABI 6 in the same way
+EXPORTS_FORCING = ["ecwam_hip_set_forcing_map", "ecwam_hip_getwnd", "ecwam_hip_cdustarz0", "ecwam_hip_wamadswstar", "ecwam_hip_getcurr", "ecwam_hip_wvblock",
+                   "ecwam_hip_fldtoifs"]
+FG_PLANES = ["UWND", "VWND", "AIRD", "WSTAR", "CICOVER", "CITHICK", "USTRA", "VSTRA", "WSWAVE", "WDWAVE", "LKFR", "UCUR", "VCUR"]      # fieldg[13][ncell]
+WVB_LWCOU2W, WVB_LWCOUHMF, WVB_LWSTOKES, WVB_LWFLUX = 1, 2, 4, 8
+MAXWVFIELDS = 32
+
+
+class ForcingOpts(C.Structure):
+    """ecwam_hip_forcing_opts: the run-time switches of GETWND that are not in Params"""
+    _fields_ = [("icode_wnd", C.c_int), ("llwswave", C.c_int), ("llwdwave", C.c_int), ("lcorrel", C.c_int), ("rwfac", C.c_double), ("iparamci", C.c_int),
+                ("lwcou", C.c_int), ("lwnemocoucic", C.c_int), ("lwnemocoucit", C.c_int), ("lnemoicerest", C.c_int), ("liceth", C.c_int), ("swamp", C.c_int),
+                ("swampcith", C.c_double), ("zmiss", C.c_double)]
+
+
 ABI_VERSION = 6        # include/ecwam_hip.h ECWAM_HIP_ABI_VERSION
 _lib = None
 
@@ -158,6 +173,15 @@ def load() -> C.CDLL:
     lib.ecwam_hip_unsetice.argtypes = [vp, ci, ci, vp, vp, cd, ci, vp]
     lib.ecwam_hip_getspec_noise.argtypes = [vp, ci, ci, vp, vp]
     lib.ecwam_hip_getspec_tail.argtypes = [vp, ci, ci, vp, vp, ci, vp]
+    for name in EXPORTS_FORCING:
+        getattr(lib, name).restype = C.c_int
+    lib.ecwam_hip_set_forcing_map.argtypes = [vp, ci, vp, ci, vp, ci]
+    lib.ecwam_hip_getwnd.argtypes = [vp, ci, ci, vp, vp, vp, vp, vp, C.POINTER(ForcingOpts), vp]
+    lib.ecwam_hip_cdustarz0.argtypes = [vp, ci, ci, vp, vp]
+    lib.ecwam_hip_wamadswstar.argtypes = [vp, ci, ci, vp, vp, vp]
+    lib.ecwam_hip_getcurr.argtypes = [vp, ci, ci, ci, vp, vp, vp, vp, vp, vp]
+    lib.ecwam_hip_wvblock.argtypes = [vp, ci, ci, vp, vp, ci, ci, cd, vp, ci, vp]
+    lib.ecwam_hip_fldtoifs.argtypes = [vp, ci, ci, vp, ci, ci, vp, vp, vp]
     _lib = lib
     return lib
 

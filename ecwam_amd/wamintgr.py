@@ -630,6 +630,71 @@ class Wamintgr:
         if not (restarted or small_domain):
             self.gfast_valid = False
 
+    # ---- the forcing and coupling seam (csrc/forcing.hip): what WAVEMDL runs immediately before and after WAMODEL, over the local rows.  The host
+    # reads the fields (GRIB, IFSTOWAM), keeps the dates and exchanges between tasks; the arithmetic on the state runs where the state lives.
+    def set_forcing_map(self, ixy_in=None, ncell_in: int = 0, ixy_out=None, ncell_out: int = 0) -> None:
+        """The cells of the local rows, 0-based: ixy_in = (JFROMIJ - NYS) nx + (IFROMIJ - NXS) into the planes of fieldg, ixy_out =
+        (NGY - KXLT) NGX + (IXLG - 1) into the outbound grid (mpfldtoifs.F90:348-350)."""
+        for m in (ixy_in, ixy_out):
+            if m is not None and np.asarray(m).size != self.n:
+                raise ValueError("set_forcing_map: one cell per local row")
+        self.ctx.set_forcing_map(ixy_in, ncell_in, ixy_out, ncell_out)
+        self.ncell_out = int(ncell_out) if ixy_out is not None else 0
+
+    def _currents(self):
+        """UCUR, VCUR of the local rows: the refraction's extended rows where there are any, else buffers of their own (zero until getcurr())"""
+        if self.irefra:
+            return self.u_ext, self.v_ext
+        if getattr(self, "ucur", None) is None:
+            self.ucur = torch.zeros(self.n, dtype=self.dtype, device=self.dev)
+            self.vcur = torch.zeros(self.n, dtype=self.dtype, device=self.dev)
+        return self.ucur, self.vcur
+
+    def getwnd(self, fieldg, target: str = "next", nemo=None, **switches) -> None:
+        """GETWND (WAMWND + MICEP) from fieldg [13][ncell_in] into FF_NEXT (target="next": NEWWIND hands it to FF_NOW later, as with a wind
+        that is read ahead) or into FF_NOW (target="now").  switches: those of HipContext.getwnd.  FF_NEXT starts as a copy of FF_NOW."""
+        if target not in ("next", "now"):
+            raise ValueError("getwnd: target is 'next' or 'now'")
+        if target == "next" and self.ff_next is None:
+            self.ff_next = self.ff.clone()
+        u, v = self._currents() if switches.get("lcorrel") else (None, None)
+        self.ctx.getwnd(0, self.n, fieldg, self.ff_next if target == "next" else self.ff, u, v, nemo, **switches)
+
+    def first_wind(self, fieldg, nemo=None, **switches) -> None:
+        """GETFRSTWND (getfrstwnd.F90:113-130): GETWND on FF_NOW, then CDUSTARZ0."""
+        self.getwnd(fieldg, "now", nemo, **switches)
+        self.ctx.cdustarz0(0, self.n, self.ff)
+
+    def adswstar(self, fieldg) -> None:
+        """WAMADSWSTAR: AIRD, WSTAR, USTRA, VSTRA of FF_NOW from fieldg."""
+        self.ctx.wamadswstar(0, self.n, fieldg, self.ff)
+
+    def getcurr(self, fieldg=None, nemo=None, mode: int = 0) -> bool:
+        """The new currents of GETCURR (mode 0 WAMCUR, 1 NEMO, 2 none).  True if any of them changed (KUPDATE): the caller then rebuilds what
+        depends on them (LLUPDTTD: the refraction terms and the advection weights)."""
+        u, v = self._currents()
+        changed = torch.zeros(1, dtype=torch.int32, device=self.dev)
+        self.ctx.getcurr(0, self.n, mode, u, v, fieldg, nemo, changed)
+        return bool(changed.item())
+
+    def wvblock(self, nwvfields: int | None = None, lwcou2w: bool = False, lwcouhmf: bool = False, lwstokes: bool = False, lwflux: bool = False,
+                prchar: float = 0.0185) -> torch.Tensor:
+        """WVBLOCK [NWVFIELDS][n] of wavemdl.F90:757-802 from FF_NOW and INTFLDS (OUTBETA with lwcou2w)."""
+        need = 1 + int(lwcouhmf) + 2 * int(lwstokes) + 7 * int(lwflux)
+        out = torch.empty((need if nwvfields is None else nwvfields, self.n), dtype=self.dtype, device=self.dev)
+        self.ctx.wvblock(0, self.n, out, self.ff, self.intf, lwcou2w, lwcouhmf, lwstokes, lwflux, prchar)
+        return out
+
+    def fldtoifs(self, wvblock, defval=None, grid=None) -> torch.Tensor:
+        """The block-to-grid step of MPFLDTOIFS on one task: grid [NWVFIELDS][ncell_out] (a new one unless given; without defval a given grid
+        keeps what the map does not reach)."""
+        if grid is None:
+            if defval is None:
+                raise ValueError("fldtoifs: a new grid needs its defaults")
+            grid = torch.empty((wvblock.shape[0], getattr(self, "ncell_out", 0)), dtype=self.dtype, device=self.dev)
+        self.ctx.fldtoifs(0, self.n, wvblock, grid, defval)
+        return grid
+
     # ---- nested grids (wamodel.F90:333-343): the caller sequences step(); bouinpt(); outbc(); outblock() as WAMODEL does.  The tables are the
     # host's (MBOUNF / MBOUNC): ijb = IJARF and ijarc = IJARC as 0-based local rows, ibcl / ibcr = IBFL / IBFR (0 = land, 1 .. NBOINP), bfw = BFW
     def set_nest_input(self, ijb, ibcl, ibcr, bfw) -> None:
