@@ -462,6 +462,98 @@ class HipContext:
         self._chk(self.lib.ecwam_hip_fldtoifs(self._h, kijs, kijl, self._real(wvblock, (nwv, ld), "WVBLOCK"), ld, nwv,
                                               None if d is None else d.ctypes.data_as(C.c_void_p), self._real(grid, (nwv, ncell), "GRID"), _stream_ptr()))
 
+    # -- GRIB-ready spectra and parameter fields (include/ecwam_hip_gribout.h; csrc/gribout.hip): from FL1 and BOUT to the encoder's VALUES
+    def set_grib_map(self, ival, ntencode: int, poles=None) -> None:
+        """ival: host integers, the 0-based position in VALUES of every row; poles: a gribout.Poles (or None: no padding).  gribout.value_map
+        builds all three from the reference's variables.  The library validates and uploads them."""
+        a = np.ascontiguousarray(ival, dtype=np.int32).reshape(-1)
+        p = None
+        if poles is not None:
+            p = _lib.GribPoles(_lib.GribPole(*poles.as_ints()[:4]), _lib.GribPole(*poles.as_ints()[4:]))
+        self._chk(self.lib.ecwam_hip_set_grib_map(self._h, a.size, a.ctypes.data_as(C.c_void_p), int(ntencode), None if p is None else C.byref(p)))
+        self._gmap = (a.size, int(ntencode))
+
+    @staticmethod
+    def _grib_opts(opts) -> _lib.GribOpts:
+        from .gribout import GRIB_DEFAULTS
+        unknown = set(opts or ()) - set(GRIB_DEFAULTS)
+        if unknown:
+            raise ValueError(f"unknown GRIB options {sorted(unknown)}")
+        o = dict(GRIB_DEFAULTS, **(opts or {}))
+        return _lib.GribOpts(float(o["ppmiss"]), float(o["ppeps"]), float(o["pprec"]), float(o["ppresol"]), float(o["ppmin_reset"]), int(o["ngrbress"]), float(o["zmiss"]))
+
+    def _grib_out(self, who, values, nfld, ppmax):
+        ntencode = getattr(self, "_gmap", (0, 0))[1]
+        return self._real(values, (nfld, ntencode), f"{who}: VALUES"), None if ppmax is None else self._real(ppmax, (nfld,), f"{who}: PPMAX")
+
+    def _fields(self, who, ifld0, nfld):
+        nfld = self.NANG * self.NR - ifld0 if nfld is None else nfld
+        if not (0 <= ifld0 and 1 <= nfld <= self.NANG * self.NR - ifld0):
+            raise ValueError(f"{who}: fields [{ifld0}, {ifld0 + nfld}) outside NANG * NFRE_RED = {self.NANG * self.NR}")
+        return int(ifld0), int(nfld)
+
+    def outspec_values(self, kijs, kijl, fl1, values, ff=None, ifld0: int = 0, nfld: int | None = None, ice_mask: bool = False, opts=None, ppmax=None):
+        """The one-task OUTSPEC on rows [kijs, kijl): fields [ifld0, ifld0 + nfld) (f = M NANG + K, M < NFRE_RED) of FL1 into values [nfld][NTENCODE]
+        through the map of set_grib_map -- ice mask (ice_mask = LICERUN .AND. LLSOURCE, reads CICOVER of ff), pole padding, LOG10 scale, threshold
+        to missing.  opts: the entries of gribout.GRIB_DEFAULTS to override; ppmax [nfld] receives PPMAX per field."""
+        ifld0, nfld = self._fields("OUTSPEC", ifld0, nfld)
+        nrow = fl1.shape[0]
+        if not (0 <= kijs <= kijl <= (nrow if ff is None else min(nrow, ff.shape[0]))):
+            raise ValueError("OUTSPEC: KIJS/KIJL outside the operands")
+        if ice_mask and ff is None:
+            raise ValueError("OUTSPEC: the ice mask reads FF")
+        o = self._grib_opts(opts)
+        pv, pm = self._grib_out("OUTSPEC", values, nfld, ppmax)
+        self._chk(self.lib.ecwam_hip_outspec_values(self._h, kijs, kijl, self._real(fl1, (nrow, self.NANG, self.NFRE), "FL1"),
+                                                    None if ff is None else self._real(ff, (ff.shape[0], NFF), "FF"), ifld0, nfld,
+                                                    _lib.OUTSPEC_ICEMASK if ice_mask else 0, C.byref(o), pv, pm, _stream_ptr()))
+
+    def outspec_pack(self, kijs, kijl, fl1, blk, ff=None, ifld0: int = 0, ice_mask: bool = False):
+        """The sending half of the many-task OUTSPEC: the ice mask, then fields [ifld0, ifld0 + blk.shape[0]) of rows [kijs, kijl) into
+        blk [nfld][ld], field-major (ZSENDBUF of outwspec.F90:186-195)."""
+        if blk.dim() != 2:
+            raise ValueError("OUTSPEC: expected BLK [nfld][ld]")
+        ifld0, nfld = self._fields("OUTSPEC", ifld0, blk.shape[0])
+        nrow, ld = fl1.shape[0], blk.shape[1]
+        if not (0 <= kijs <= kijl <= min(ld, nrow if ff is None else min(nrow, ff.shape[0]))):
+            raise ValueError("OUTSPEC: KIJS/KIJL outside the operands")
+        if ice_mask and ff is None:
+            raise ValueError("OUTSPEC: the ice mask reads FF")
+        self._chk(self.lib.ecwam_hip_outspec_pack(self._h, kijs, kijl, self._real(fl1, (nrow, self.NANG, self.NFRE), "FL1"),
+                                                  None if ff is None else self._real(ff, (ff.shape[0], NFF), "FF"), ifld0, nfld,
+                                                  _lib.OUTSPEC_ICEMASK if ice_mask else 0, self._real(blk, (nfld, ld), "BLK"), ld, _stream_ptr()))
+
+    def grib_values(self, kijs, kijl, src, values, spectral: bool, columns=None, opts=None, ppmax=None):
+        """MAKEGRID + WGRIBENCODE_VALUES on rows [kijs, kijl) of block vectors.  Without columns, src is [nfld][ld] field-major (the gathered
+        ZRECVBUF, or the blk of outspec_pack); with columns, src is [npts][ncol] point-major (BOUT) and columns lists the ones to take, in the
+        order of values: one call goes to the library per run of consecutive columns.  spectral: the LOG10 scale and the threshold as well."""
+        if src.dim() != 2 or not (src.is_cuda and src.dtype == self.dtype and src.is_contiguous()):
+            raise ValueError(f"GRIB_VALUES: expected a contiguous two-dimensional {self.dtype} cuda tensor")
+        o = self._grib_opts(opts)
+        rb = self.real_bytes
+        if columns is None:
+            nfld, ld = src.shape
+            runs = [(0, 0, nfld)]
+            fs, ps, rows = ld, 1, ld
+        else:
+            cols = [int(c) for c in columns]
+            rows, ncol = src.shape
+            if not cols or min(cols) < 0 or max(cols) >= ncol:
+                raise ValueError("GRIB_VALUES: a column outside the source")
+            nfld, fs, ps = len(cols), 1, ncol
+            runs, a = [], 0      # (first field of values, first column of src, length)
+            for i in range(1, nfld + 1):
+                if i == nfld or cols[i] != cols[i - 1] + 1:
+                    runs.append((a, cols[a], i - a))
+                    a = i
+        if not (0 <= kijs <= kijl <= rows):
+            raise ValueError("GRIB_VALUES: KIJS/KIJL outside the operands")
+        pv, pm = self._grib_out("GRIB_VALUES", values, nfld, ppmax if spectral else None)
+        ntencode = self._gmap[1] if hasattr(self, "_gmap") else 0
+        for f0, c0, n in runs:
+            self._chk(self.lib.ecwam_hip_grib_values(self._h, kijs, kijl, src.data_ptr() + c0 * rb, fs, ps, n, 1 if spectral else 0, C.byref(o),
+                                                     pv + f0 * ntencode * rb, None if pm is None else pm + f0 * rb, _stream_ptr()))
+
     # -- nested grids: BOUINPT / INTSPEC (bouinpt.F90:385-424) and OUTBC (outbc.F90:78-91), the two calls of wamodel.F90:333-343
     def bouinpt(self, kijs, kijl, ijb, ibcl, ibcr, bfw, f1, par1, fl1, par_out=None):
         """The coarse model's boundary spectra into the rows ijb (0-based, distinct) of FL1 that lie in [kijs, kijl): ibcl / ibcr = IBFL / IBFR

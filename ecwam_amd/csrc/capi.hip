@@ -97,9 +97,23 @@ struct ecwam_hip_ctx {
   int* fmap_out = nullptr;
   int fmap_n = 0;
   size_t fmap_ncell_in = 0, fmap_ncell_out = 0;
+  // ecwam_hip_set_grib_map (csrc/gribout.hip): the validated map on the device (gmap.ival == nullptr: none), its rows, the scratch of the maxima
+  GribMapDev gmap = {};
+  int gmap_n = 0;
+  void* gmap_keys = nullptr;
   const void* obs = nullptr;  // LSUBGRID: device OBS[n_obs][8][NFRE] (ecwam_hip_set_obstructions), read by CTUW / PROPAGS2
   int n_obs = 0;
 };
+
+static void grib_map_free(ecwam_hip_ctx* c) {
+  if (c->gmap.ival) (void)hipFree(const_cast<int*>(c->gmap.ival));
+  if (c->gmap.unfilled) (void)hipFree(const_cast<int*>(c->gmap.unfilled));
+  if (c->gmap.adj) (void)hipFree(const_cast<int*>(c->gmap.adj));
+  if (c->gmap_keys) (void)hipFree(c->gmap_keys);
+  c->gmap = GribMapDev{};
+  c->gmap_n = 0;
+  c->gmap_keys = nullptr;
+}
 
 // f(T()) with T = the working precision of the context, float or double: every launch is written once, as launch_x<decltype(t)>(...)
 template <typename F>
@@ -530,6 +544,7 @@ int ecwam_hip_destroy(ecwam_hip_ctx* c) {
   if (c->adv_dir) (void)hipFree(c->adv_dir);
   if (c->fmap_in) (void)hipFree(c->fmap_in);
   if (c->fmap_out) (void)hipFree(c->fmap_out);
+  grib_map_free(c);
   halo_release(c);
   delete c;
   return 0;
@@ -1053,6 +1068,128 @@ int ecwam_hip_fldtoifs(ecwam_hip_ctx* c, int kijs, int kijl, const void* wvblock
   if (defval && !grid) return fail(who + ": null pointer");
   in_precision(c, [&](auto t) {
     launch_fldtoifs<decltype(t)>(kijs, kijl, c->fmap_out, wvblock, ld, nwvfields, defval, grid, c->fmap_ncell_out, (hipStream_t)stream);
+  });
+  return launched();
+}
+
+// GRIB-ready spectra and parameter fields (include/ecwam_hip_gribout.h; csrc/gribout.hip)
+int ecwam_hip_set_grib_map(ecwam_hip_ctx* c, int npts, const int* ival, int ntencode, const ecwam_hip_grib_poles* poles) {
+  if (!c) return fail("null context");
+  const std::string who = "ecwam_hip_set_grib_map";
+  if (npts < 0) return fail(who + ": negative count");
+  if (ntencode < 1) return fail(who + ": NTENCODE must be at least 1");
+  if (npts > 0 && !ival) return fail(who + ": null pointer");
+  // the four ranges: inside the vector, no two overlapping; a pole without padding takes no part
+  ecwam_hip_grib_pole pl[2] = {};
+  if (poles) { pl[0] = poles->north; pl[1] = poles->south; }
+  int lo[4], hi[4], nr = 0;
+  for (int s = 0; s < 2; s++) {
+    if (pl[s].npole < 0 || pl[s].nadj < 0) return fail(who + ": a pole range has a negative length");
+    if (pl[s].npole == 0) { pl[s] = ecwam_hip_grib_pole{}; continue; }
+    const int r0[2] = {pl[s].pole0, pl[s].adj0}, rn[2] = {pl[s].npole, pl[s].nadj};
+    for (int q = 0; q < 2; q++) {
+      if (r0[q] < 0 || r0[q] > ntencode || rn[q] > ntencode - r0[q]) return fail(who + ": a pole range leaves the vector");
+      if (rn[q] == 0) continue;
+      for (int o = 0; o < nr; o++)
+        if (r0[q] < hi[o] && lo[o] < r0[q] + rn[q]) return fail(who + ": the pole ranges overlap");
+      lo[nr] = r0[q]; hi[nr] = r0[q] + rn[q]; nr++;
+    }
+  }
+  std::vector<int> inv((size_t)ntencode, -1);      // cell -> row
+  for (int i = 0; i < npts; i++) {
+    if (ival[i] < 0 || ival[i] >= ntencode) return fail(who + ": index " + std::to_string(i) + " outside [0, ntencode)");
+    if (inv[ival[i]] >= 0) return fail(who + ": index " + std::to_string(i) + " is a duplicate (two rows would write one value)");
+    inv[ival[i]] = i;
+  }
+  auto in_pole = [&](int cell) { return (cell >= pl[0].pole0 && cell - pl[0].pole0 < pl[0].npole) || (cell >= pl[1].pole0 && cell - pl[1].pole0 < pl[1].npole); };
+  std::vector<int> unf, adj;
+  for (int cell = 0; cell < ntencode; cell++)
+    if (inv[cell] < 0 && !in_pole(cell)) unf.push_back(cell);
+  for (int s = 0; s < 2; s++)
+    for (int i = 0; i < pl[s].nadj; i++) adj.push_back(inv[pl[s].adj0 + i]);
+  HIPCHK(hipSetDevice(c->device));
+  // a copy another stream may still read is not freed under it
+  HIPCHK(hipDeviceSynchronize());
+  grib_map_free(c);
+  auto upload = [](const int* h, size_t n, const int** d) -> hipError_t {
+    int* p = nullptr;
+    hipError_t e = hipMalloc((void**)&p, (n > 0 ? n : 1) * sizeof(int));
+    if (e == hipSuccess && n > 0) e = hipMemcpy(p, h, n * sizeof(int), hipMemcpyHostToDevice);
+    *d = p;
+    return e;
+  };
+  HIPCHK(upload(ival, (size_t)npts, &c->gmap.ival));
+  HIPCHK(upload(unf.data(), unf.size(), &c->gmap.unfilled));
+  HIPCHK(upload(adj.data(), adj.size(), &c->gmap.adj));
+  HIPCHK(hipMalloc(&c->gmap_keys, (size_t)c->NANG * c->NFRE_RED * sizeof(unsigned long long)));
+  c->gmap.nunf = (int)unf.size(); c->gmap.ntencode = ntencode; c->gmap.north = pl[0]; c->gmap.south = pl[1];
+  c->gmap_n = npts;
+  return 0;
+}
+// the checks of the three calls on rows, in the order of seam_checks; need_map: rows beyond the map are a bad range
+static int grib_checks(ecwam_hip_ctx* c, const std::string& who, int kijs, int kijl, bool need_map, std::initializer_list<SeamBuf> bufs) {
+  if (kijl < kijs || kijs < 0) return fail(who + ": bad range");
+  if (need_map && !c->gmap.ival) return fail(who + ": no grib map");
+  if (need_map && kijl > c->gmap_n) return fail(who + ": bad range");
+  HIPCHK(hipSetDevice(c->device));
+  for (const SeamBuf& b : bufs)
+    if (kijl > kijs && b.used && !b.p) return fail(who + ": null pointer");
+  for (const SeamBuf& b : bufs)
+    if (b.used && ((uintptr_t)b.p % 16) != 0) return fail(who + ": the buffers must be 16-byte aligned");
+  return 0;
+}
+static int grib_opts_ok(const std::string& who, const ecwam_hip_grib_opts* o, bool spectral) {
+  if (!o) return fail(who + ": null options");
+  if (spectral && (o->ngrbress < 1 || o->ngrbress > 30)) return fail(who + ": NGRBRESS outside 1 .. 30");
+  if (spectral && !(o->ppeps > 0)) return fail(who + ": PPEPS must be positive");
+  return 0;
+}
+static int grib_tile_done(const std::string& who, int rc) {
+  if (rc == 0) return launched();
+  if (rc < 0) return fail(who + ": the frequencies of a direction are no whole number of 16-byte chunks");
+  return fail(who + ": unsupported spectral size");
+}
+int ecwam_hip_outspec_values(ecwam_hip_ctx* c, int kijs, int kijl, const void* fl1, const void* ff, int ifld0, int nfld, int flags, const ecwam_hip_grib_opts* o,
+                             void* values, void* ppmax, void* stream) {
+  if (!c) return fail("null context");
+  const std::string who = "ecwam_hip_outspec_values";
+  if (int rc = grib_opts_ok(who, o, true)) return rc;
+  if (flags & ~ECWAM_HIP_OUTSPEC_ICEMASK) return fail(who + ": unknown flags");
+  if (ifld0 < 0 || nfld < 1 || nfld > c->NANG * c->NFRE_RED - ifld0) return fail(who + ": bad field range");
+  const bool ice = (flags & ECWAM_HIP_OUTSPEC_ICEMASK) != 0;
+  if (int rc = grib_checks(c, who, kijs, kijl, true, {{fl1, true}, {ff, ice}, {values, true}, {ppmax, false}})) return rc;
+  if (((uintptr_t)ppmax % 16) != 0) return fail(who + ": the buffers must be 16-byte aligned");
+  return grib_tile_done(who, in_precision(c, [&](auto t) {
+    return launch_outspec_values<decltype(t)>(kijs, kijl, fl1, ff, ifld0, nfld, ice, c->p.cithrsh, c->p.flmin, *o, c->gmap, values, ppmax, c->gmap_keys, c->NANG, c->NFRE,
+                                              c->NFRE_RED, (hipStream_t)stream);
+  }));
+}
+int ecwam_hip_outspec_pack(ecwam_hip_ctx* c, int kijs, int kijl, const void* fl1, const void* ff, int ifld0, int nfld, int flags, void* blk, int ld, void* stream) {
+  if (!c) return fail("null context");
+  const std::string who = "ecwam_hip_outspec_pack";
+  if (flags & ~ECWAM_HIP_OUTSPEC_ICEMASK) return fail(who + ": unknown flags");
+  if (ifld0 < 0 || nfld < 1 || nfld > c->NANG * c->NFRE_RED - ifld0) return fail(who + ": bad field range");
+  const bool ice = (flags & ECWAM_HIP_OUTSPEC_ICEMASK) != 0;
+  if (int rc = grib_checks(c, who, kijs, kijl, false, {{fl1, true}, {ff, ice}, {blk, true}})) return rc;
+  if (ld < kijl) return fail(who + ": bad range");
+  return grib_tile_done(who, in_precision(c, [&](auto t) {
+    return launch_outspec_pack<decltype(t)>(kijs, kijl, fl1, ff, ifld0, nfld, ice, c->p.cithrsh, c->p.flmin, blk, ld, c->NANG, c->NFRE, c->NFRE_RED, (hipStream_t)stream);
+  }));
+}
+int ecwam_hip_grib_values(ecwam_hip_ctx* c, int kijs, int kijl, const void* src, long long fstride, long long pstride, int nfld, int spectral,
+                          const ecwam_hip_grib_opts* o, void* values, void* ppmax, void* stream) {
+  if (!c) return fail("null context");
+  const std::string who = "ecwam_hip_grib_values";
+  if (spectral != 0 && spectral != 1) return fail(who + ": spectral must be 0 or 1");
+  if (int rc = grib_opts_ok(who, o, spectral != 0)) return rc;
+  if (nfld < 1 || nfld > (spectral ? c->NANG * c->NFRE_RED : 65535)) return fail(who + ": bad field range");
+  if (fstride < 1 || pstride < 1) return fail(who + ": the strides must be positive");
+  if (int rc = grib_checks(c, who, kijs, kijl, true, {})) return rc;
+  if (kijl > kijs && (!src || !values)) return fail(who + ": null pointer");
+  // the stores are single reals: a run of columns may begin anywhere in values
+  if (((uintptr_t)src | (uintptr_t)values | (uintptr_t)ppmax) % c->real_bytes != 0) return fail(who + ": the buffers must be aligned to a real");
+  in_precision(c, [&](auto t) {
+    launch_grib_values<decltype(t)>(kijs, kijl, src, fstride, pstride, nfld, spectral, *o, c->gmap, values, ppmax, c->gmap_keys, (hipStream_t)stream);
   });
   return launched();
 }

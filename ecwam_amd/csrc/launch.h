@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/ecwam_hip_forcing.h"
+#include "../../include/ecwam_hip_gribout.h"
 #include "implsch_adv_args.h"
 
 // The grid geometry the advection kernels form the CTU weights from, in the untyped form and the order of the C interface's arguments
@@ -131,6 +132,22 @@ template <typename T> void launch_wvblock(const void* tab, int llgcbz0, int kijs
         void* wvblock, int ld, hipStream_t s);
 template <typename T> void launch_fldtoifs(int kijs, int kijl, const int* map, const void* wvblock, int ld, int nwvfields, const double* defval, void* grid, size_t ncell,
         hipStream_t s);
+
+// ---- gribout.hip: GRIB-ready spectra and parameter fields (include/ecwam_hip_gribout.h).  GribMapDev = the validated map of ecwam_hip_set_grib_map on the
+// device: ival [npts] row -> cell, unfilled [nunf] the cells no row fills (those of a padded pole row excepted), adj [north.nadj + south.nadj] cell -> row
+// or -1 for the rows beside the poles; a pole without padding has npole = nadj = 0.  keys = the scratch of the per-field maxima.  The tile launchers return
+// 0 = launched (or nothing to do), 1 = the tile does not fit the LDS, -1 = NFRE is no whole number of 16-byte pieces. ------------------------------------
+struct GribMapDev {
+  const int *ival, *unfilled, *adj;
+  int nunf, ntencode;
+  ecwam_hip_grib_pole north, south;
+};
+template <typename T> int launch_outspec_values(int kijs, int kijl, const void* fl1, const void* ff, int ifld0, int nfld, int ice, double cithrsh, double flmin,
+        const ecwam_hip_grib_opts& o, const GribMapDev& g, void* values, void* ppmax, void* keys, int NANG, int NFRE, int NFRE_RED, hipStream_t s);
+template <typename T> int launch_outspec_pack(int kijs, int kijl, const void* fl1, const void* ff, int ifld0, int nfld, int ice, double cithrsh, double flmin, void* blk,
+        int ld, int NANG, int NFRE, int NFRE_RED, hipStream_t s);
+template <typename T> void launch_grib_values(int kijs, int kijl, const void* src, long long fstride, long long pstride, int nfld, int spectral,
+        const ecwam_hip_grib_opts& o, const GribMapDev& g, void* values, void* ppmax, void* keys, hipStream_t s);
 
 // ---- outblock.hip: OUTBLOCK itself (outblock.F90:159-610) -- the plan of ecwam_hip_set_outblock and the kernel that fills BOUT ---------------------
 // where a BOUT column comes from: the packed buffers of the output calls (in the work space of the context), the caller's per-point arrays, or nothing

@@ -81,6 +81,27 @@ class ForcingOpts(C.Structure):
                 ("swampcith", C.c_double), ("zmiss", C.c_double)]
 
 
+# include/ecwam_hip_gribout.h: GRIB-ready spectra and parameter fields (OUTSPEC, OUTINT), added to ABI 6 in the same way
+EXPORTS_GRIBOUT = ["ecwam_hip_set_grib_map", "ecwam_hip_outspec_values", "ecwam_hip_outspec_pack", "ecwam_hip_grib_values"]
+OUTSPEC_ICEMASK = 1
+
+
+class GribPole(C.Structure):
+    """ecwam_hip_grib_pole"""
+    _fields_ = [("pole0", C.c_int), ("npole", C.c_int), ("adj0", C.c_int), ("nadj", C.c_int)]
+
+
+class GribPoles(C.Structure):
+    """ecwam_hip_grib_poles"""
+    _fields_ = [("north", GribPole), ("south", GribPole)]
+
+
+class GribOpts(C.Structure):
+    """ecwam_hip_grib_opts: YOWGRIBHD's packing constants and ZMISS"""
+    _fields_ = [("ppmiss", C.c_double), ("ppeps", C.c_double), ("pprec", C.c_double), ("ppresol", C.c_double), ("ppmin_reset", C.c_double), ("ngrbress", C.c_int),
+                ("zmiss", C.c_double)]
+
+
 ABI_VERSION = 6        # include/ecwam_hip.h ECWAM_HIP_ABI_VERSION
 _lib = None
 
@@ -182,6 +203,13 @@ def load() -> C.CDLL:
     lib.ecwam_hip_getcurr.argtypes = [vp, ci, ci, ci, vp, vp, vp, vp, vp, vp]
     lib.ecwam_hip_wvblock.argtypes = [vp, ci, ci, vp, vp, ci, ci, cd, vp, ci, vp]
     lib.ecwam_hip_fldtoifs.argtypes = [vp, ci, ci, vp, ci, ci, vp, vp, vp]
+    for name in EXPORTS_GRIBOUT:
+        getattr(lib, name).restype = C.c_int
+    ll = C.c_longlong
+    lib.ecwam_hip_set_grib_map.argtypes = [vp, ci, vp, ci, C.POINTER(GribPoles)]
+    lib.ecwam_hip_outspec_values.argtypes = [vp, ci, ci, vp, vp, ci, ci, ci, C.POINTER(GribOpts), vp, vp, vp]
+    lib.ecwam_hip_outspec_pack.argtypes = [vp, ci, ci, vp, vp, ci, ci, ci, vp, ci, vp]
+    lib.ecwam_hip_grib_values.argtypes = [vp, ci, ci, vp, ll, ll, ci, ci, C.POINTER(GribOpts), vp, vp, vp]
     _lib = lib
     return lib
 

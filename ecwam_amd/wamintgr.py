@@ -695,6 +695,49 @@ class Wamintgr:
         self.ctx.fldtoifs(0, self.n, wvblock, grid, defval)
         return grid
 
+    # ---- GRIB-ready output (csrc/gribout.hip): OUTSPEC and OUTINT up to the vector VALUES the encoder takes.  eccodes, the dates, the exchange
+    # between tasks and FDB stay with the host.
+    def set_grib_map(self, ival=None, ntencode: int | None = None, poles=None, lpadpoles: bool = True) -> None:
+        """Without arguments: the map of this instance's rows on its own grid (a reduced grid, IRGG = 1, CLDOMAIN = 'g'), from gribout.value_map.
+        The poles are padded only where one instance owns the whole grid: a pole mean across a decomposition belongs to the encoding task."""
+        if ival is None:
+            from . import gribout
+            g, d = self.grid, self.dom
+            amonop = float(g.amosop) + (g.ngy - 1) * float(g.xdella)
+            ival, ntencode, poles = gribout.value_map(g.nlonrgg, g.ixlg[d.lo:d.hi] + 1, g.kxlt[d.lo:d.hi] + 1, g.ngy, 1, amonop, g.amosop, g.xdella, "g",
+                                                      lpadpoles and d.nranks == 1)
+        if np.asarray(ival).size != self.n:
+            raise ValueError("set_grib_map: one value position per local row")
+        self.ctx.set_grib_map(ival, ntencode, poles)
+        self.ntencode = int(ntencode)
+
+    def outspec(self, fields=None, ice_mask: bool = True, opts=None, values=None, ppmax=None):
+        """OUTSPEC on one task: (values [nfld][NTENCODE], ppmax [nfld]) of the fields (ifld0, nfld) -- default all NANG * NFRE_RED -- of FL1.
+        ice_mask is LLSOURCE: the mask applies when the run has LICERUN.  values / ppmax: buffers to write into (new ones otherwise)."""
+        if getattr(self, "ntencode", None) is None:
+            raise RuntimeError("outspec: set_grib_map() first")
+        ifld0, nfld = (0, self.cfg.nang * self.cfg.nfre_red) if fields is None else (int(fields[0]), int(fields[1]))
+        if values is None:
+            values = torch.empty((nfld, self.ntencode), dtype=self.dtype, device=self.dev)
+        if ppmax is None:
+            ppmax = torch.empty(nfld, dtype=self.dtype, device=self.dev)
+        self.ctx.outspec_values(0, self.n, self.fl1, values, self.ff, ifld0, nfld, bool(ice_mask and self.cfg.licerun), opts, ppmax)
+        return values, ppmax
+
+    def outint(self, columns, opts=None, values=None) -> torch.Tensor:
+        """OUTINT's path for the BOUT that the last outblock() left: values [len(columns)][NTENCODE]; columns are parameter numbers or short
+        names of api.OUTBLOCK_PARAMS that the request held."""
+        if getattr(self, "ntencode", None) is None:
+            raise RuntimeError("outint: set_grib_map() first")
+        if getattr(self, "_bout", None) is None:
+            raise RuntimeError("outint: outblock() first")
+        bout, where = self._bout
+        cols = [where[api.OUTBLOCK_NUMBER[c] if isinstance(c, str) else int(c)] for c in columns]
+        if values is None:
+            values = torch.empty((len(cols), self.ntencode), dtype=self.dtype, device=self.dev)
+        self.ctx.grib_values(0, self.n, bout, values, False, columns=cols, opts=opts)
+        return values
+
     # ---- nested grids (wamodel.F90:333-343): the caller sequences step(); bouinpt(); outbc(); outblock() as WAMODEL does.  The tables are the
     # host's (MBOUNF / MBOUNC): ijb = IJARF and ijarc = IJARC as 0-based local rows, ibcl / ibcr = IBFL / IBFR (0 = land, 1 .. NBOINP), bfw = BFW
     def set_nest_input(self, ijb, ibcl, ibcr, bfw) -> None:
@@ -819,6 +862,7 @@ class Wamintgr:
         iodp = torch.ones(self.n, dtype=torch.int32, device=self.dev)
         self.ctx.outblock(0, self.n, bout, fl1=self.fl1, xllws=self.xllws, mij=self.mij, wvprpt=self.wvprpt, ff=self.ff, intf=self.intf, ucur=u, vcur=v,
                           iodp=iodp, ibrmem=self.intf[:, 15].contiguous())
+        self._bout = (bout, dict(self._outblock_columns))      # outint() takes its columns from here
         return bout, dict(self._outblock_columns)
 
     def swh_norm(self):
