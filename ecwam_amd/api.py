@@ -554,6 +554,35 @@ class HipContext:
             self._chk(self.lib.ecwam_hip_grib_values(self._h, kijs, kijl, src.data_ptr() + c0 * rb, fs, ps, n, 1 if spectral else 0, C.byref(o),
                                                      pv + f0 * ntencode * rb, None if pm is None else pm + f0 * rb, _stream_ptr()))
 
+    # -- the warm start (include/ecwam_hip_gribin.h; csrc/gribin.hip): decoded GRIB spectra and READFL's record into FL1
+    def _getspec(self, call, who, kijs, kijl, src, stride_min, fl1, ifld0, fmax, unscale, missing, opts):
+        if src.dim() != 2 or not (src.is_cuda and src.dtype == self.dtype and src.is_contiguous()):
+            raise ValueError(f"{who}: expected a contiguous two-dimensional {self.dtype} cuda tensor of field vectors")
+        nfld, stride = src.shape
+        if not (0 <= ifld0 and 1 <= nfld <= fmax - ifld0):
+            raise ValueError(f"{who}: fields [{ifld0}, {ifld0 + nfld}) outside [0, {fmax})")
+        nrow = fl1.shape[0]
+        if not (0 <= kijs <= kijl <= nrow) or stride < stride_min:
+            raise ValueError(f"{who}: KIJS/KIJL outside the operands, or vectors shorter than {stride_min}")
+        flags = (_lib.GETSPEC_UNSCALE if unscale else 0) | (_lib.GETSPEC_MISSING if missing else 0)
+        o = self._grib_opts(opts)
+        self._chk(call(self._h, kijs, kijl, src.data_ptr(), stride, int(ifld0), nfld, flags, C.byref(o) if flags else None,
+                       self._real(fl1, (nrow, self.NANG, self.NFRE), "FL1"), _stream_ptr()))
+
+    def getspec_values(self, kijs, kijl, values, fl1, ifld0: int = 0, unscale: bool = True, missing: bool = True, opts=None):
+        """GETSPEC's GRIB read on one task for rows [kijs, kijl): values [nfld][>= NTENCODE], the decoded vectors of the fields
+        [ifld0, ifld0 + nfld) (f = M NANG + K, M < NFRE_RED) as eccodes returned them, through the map of set_grib_map into FL1[ij][K][M].
+        unscale: 10**(v - |PPREC|) - PPEPS where v /= ZMISS (grib2wgrid.F90:771-775); missing: then ZMISS -> EPSMIN (getspec.F90:550-552).
+        Every other element of FL1 keeps its bits; getspec_tail follows the last field."""
+        self._getspec(self.lib.ecwam_hip_getspec_values, "GETSPEC", kijs, kijl, values, getattr(self, "_gmap", (0, 0))[1], fl1, ifld0,
+                      self.NANG * self.NR, unscale, missing, opts)
+
+    def getspec_unpack(self, kijs, kijl, blk, fl1, ifld0: int = 0, unscale: bool = False, missing: bool = False, opts=None):
+        """The receiving half of GETSPEC on many tasks (ZRECVBUF, getspec.F90:602-619) and READFL's record: blk [nfld][ld], row ij at index ij
+        (the convention of outspec_pack), fields [ifld0, ifld0 + nfld) up to NANG * NFRE, into FL1[ij][K][M] for rows [kijs, kijl).  Without
+        flags the values pass as they are (the restart record)."""
+        self._getspec(self.lib.ecwam_hip_getspec_unpack, "GETSPEC", kijs, kijl, blk, kijl, fl1, ifld0, self.NANG * self.NFRE, unscale, missing, opts)
+
     # -- nested grids: BOUINPT / INTSPEC (bouinpt.F90:385-424) and OUTBC (outbc.F90:78-91), the two calls of wamodel.F90:333-343
     def bouinpt(self, kijs, kijl, ijb, ibcl, ibcr, bfw, f1, par1, fl1, par_out=None):
         """The coarse model's boundary spectra into the rows ijb (0-based, distinct) of FL1 that lie in [kijs, kijl): ibcl / ibcr = IBFL / IBFR

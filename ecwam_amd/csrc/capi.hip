@@ -1194,6 +1194,35 @@ int ecwam_hip_grib_values(ecwam_hip_ctx* c, int kijs, int kijl, const void* src,
   return launched();
 }
 
+// Decoded GRIB spectra and READFL's record into FL1 (include/ecwam_hip_gribin.h; csrc/gribin.hip).  map: the _values form (through the map of
+// ecwam_hip_set_grib_map, fields below NANG NFRE_RED, stride >= ntencode); otherwise the _unpack form (fields below NANG NFRE, stride >= kijl)
+static int getspec_fields(ecwam_hip_ctx* c, const std::string& who, bool map, int kijs, int kijl, const void* src, long long stride, int ifld0, int nfld, int flags,
+                          const ecwam_hip_grib_opts* o, void* fl1, void* stream) {
+  if (flags & ~(ECWAM_HIP_GETSPEC_UNSCALE | ECWAM_HIP_GETSPEC_MISSING)) return fail(who + ": unknown flags");
+  if (flags && !o) return fail(who + ": null options");
+  const int mlim = map ? c->NFRE_RED : c->NFRE;
+  if (ifld0 < 0 || nfld < 1 || nfld > c->NANG * mlim - ifld0) return fail(who + ": bad field range");
+  if (int rc = grib_checks(c, who, kijs, kijl, map, {})) return rc;
+  if (stride < (map ? (long long)c->gmap.ntencode : (long long)kijl)) return fail(who + ": bad range");
+  if (kijl > kijs && (!src || !fl1)) return fail(who + ": null pointer");
+  if (((uintptr_t)fl1 % 16) != 0) return fail(who + ": the spectra must be 16-byte aligned");
+  if (((uintptr_t)src % c->real_bytes) != 0) return fail(who + ": the buffers must be aligned to a real");
+  return grib_tile_done(who, in_precision(c, [&](auto t) {
+    return launch_getspec_fields<decltype(t)>(kijs, kijl, src, stride, map ? c->gmap.ival : nullptr, ifld0, nfld, flags, o, c->p.epsmin, fl1, c->NANG, c->NFRE, mlim,
+                                              (hipStream_t)stream);
+  }));
+}
+int ecwam_hip_getspec_values(ecwam_hip_ctx* c, int kijs, int kijl, const void* values, long long fstride, int ifld0, int nfld, int flags, const ecwam_hip_grib_opts* o,
+                             void* fl1, void* stream) {
+  if (!c) return fail("null context");
+  return getspec_fields(c, "ecwam_hip_getspec_values", true, kijs, kijl, values, fstride, ifld0, nfld, flags, o, fl1, stream);
+}
+int ecwam_hip_getspec_unpack(ecwam_hip_ctx* c, int kijs, int kijl, const void* blk, long long ld, int ifld0, int nfld, int flags, const ecwam_hip_grib_opts* o, void* fl1,
+                             void* stream) {
+  if (!c) return fail("null context");
+  return getspec_fields(c, "ecwam_hip_getspec_unpack", false, kijs, kijl, blk, ld, ifld0, nfld, flags, o, fl1, stream);
+}
+
 // bit 0: the one-kernel step covers the context; bit 1: also with fast-wave sub-steps (gin); bit 2: also with the obstructions of
 // ecwam_hip_set_obstructions -- a caller takes the one-kernel step when the bits of what it needs are set
 int ecwam_hip_propags2_implsch_supported(ecwam_hip_ctx* c) { return c && fused_ok(c) ? implsch4_adv_forms(c->NANG, c->real_bytes) : 0; }

@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/ecwam_hip_forcing.h"
+#include "../../include/ecwam_hip_gribin.h"
 #include "../../include/ecwam_hip_gribout.h"
 #include "implsch_adv_args.h"
 
@@ -148,6 +149,11 @@ template <typename T> int launch_outspec_pack(int kijs, int kijl, const void* fl
         int ld, int NANG, int NFRE, int NFRE_RED, hipStream_t s);
 template <typename T> void launch_grib_values(int kijs, int kijl, const void* src, long long fstride, long long pstride, int nfld, int spectral,
         const ecwam_hip_grib_opts& o, const GribMapDev& g, void* values, void* ppmax, void* keys, hipStream_t s);
+
+// ---- gribin.hip: decoded GRIB spectra and READFL's record into FL1 (include/ecwam_hip_gribin.h).  ival = the map row -> position in a vector, or nullptr: the
+// row itself (the unpack form); src[nfld][stride]; mlim = the frequencies a field may have (NFRE_RED / NFRE).  Returns as the tile launchers above. ----------
+template <typename T> int launch_getspec_fields(int kijs, int kijl, const void* src, long long stride, const int* ival, int ifld0, int nfld, int flags,
+        const ecwam_hip_grib_opts* o, double epsmin, void* fl1, int NANG, int NFRE, int mlim, hipStream_t s);
 
 // ---- outblock.hip: OUTBLOCK itself (outblock.F90:159-610) -- the plan of ecwam_hip_set_outblock and the kernel that fills BOUT ---------------------
 // where a BOUT column comes from: the packed buffers of the output calls (in the work space of the context), the caller's per-point arrays, or nothing

@@ -38,6 +38,30 @@ def _nint(x: float) -> int:
     return int(np.floor(abs(x) + 0.5)) * (1 if x >= 0 else -1)
 
 
+def read_map(nlonrgg, ixlg, kxlt, ngy):
+    """(ival, nvalues) of the READ of a GRIB spectrum (include/ecwam_hip_gribin.h): where in the decoded vector GRIB2WGRID's full copy
+    (grib2wgrid.F90:793-802: row K = 1 .. NGY of FIELD takes the next NLONRGG(NGY - K + 1) values, from the first value on -- there is no
+    start offset) and GETSPEC's gather WORK(IJ) = FIELD(IXLG, NGY - KXLT + 1) (getspec.F90:458-462) find point ij; nvalues is the number of
+    values the copy consumes.  Equal to the ival of value_map wherever the output's ICOUNT is 1 (IRGG = 1, or CLDOMAIN = 'm'); a message
+    laid out otherwise is read with this map set (ecwam_hip_set_grib_map(ival, ntencode >= nvalues, no poles)) and the output map set
+    afterwards."""
+    nlonrgg = np.asarray(nlonrgg, dtype=np.int64).reshape(-1)
+    ixlg = np.asarray(ixlg, dtype=np.int64).reshape(-1)
+    kxlt = np.asarray(kxlt, dtype=np.int64).reshape(-1)
+    ngy = int(ngy)
+    if nlonrgg.size != ngy or ngy < 1 or (nlonrgg < 1).any():
+        raise ValueError(f"read_map: NLONRGG must hold NGY = {ngy} positive row lengths")
+    if ixlg.size != kxlt.size:
+        raise ValueError("read_map: IXLG and KXLT differ in length")
+    if kxlt.size and (kxlt.min() < 1 or kxlt.max() > ngy):
+        raise ValueError("read_map: KXLT outside 1 .. NGY")
+    if ixlg.size and (ixlg.min() < 1 or (ixlg > nlonrgg[kxlt - 1]).any()):
+        raise ValueError("read_map: IXLG outside 1 .. NLONRGG(KXLT)")
+    length = nlonrgg[::-1]      # by K - 1
+    start = np.concatenate([[0], np.cumsum(length)[:-1]])
+    return (start[ngy - kxlt] + ixlg - 1).astype(np.int32), int(length.sum())
+
+
 def value_map(nlonrgg, ixlg, kxlt, ngy, irgg, amonop, amosop, xdella, cldomain="g", lpadpoles=True):
     """(ival, ntencode, poles) from the reference's variables: NLONRGG(1:NGY) south to north, BLK2GLO%IXLG and %KXLT of the points (1-based, as
     the reference holds them), IRGG, AMONOP, AMOSOP, XDELLA, CLDOMAIN, LPADPOLES.  ival[ij] is the 0-based position in VALUES of point ij;

@@ -102,6 +102,10 @@ class GribOpts(C.Structure):
                 ("zmiss", C.c_double)]
 
 
+# include/ecwam_hip_gribin.h: decoded GRIB spectra and READFL's record into FL1 (GETSPEC's warm start), added to ABI 6 in the same way
+EXPORTS_GRIBIN = ["ecwam_hip_getspec_values", "ecwam_hip_getspec_unpack"]
+GETSPEC_UNSCALE, GETSPEC_MISSING = 1, 2
+
 ABI_VERSION = 6        # include/ecwam_hip.h ECWAM_HIP_ABI_VERSION
 _lib = None
 
@@ -210,6 +214,9 @@ def load() -> C.CDLL:
     lib.ecwam_hip_outspec_values.argtypes = [vp, ci, ci, vp, vp, ci, ci, ci, C.POINTER(GribOpts), vp, vp, vp]
     lib.ecwam_hip_outspec_pack.argtypes = [vp, ci, ci, vp, vp, ci, ci, ci, vp, ci, vp]
     lib.ecwam_hip_grib_values.argtypes = [vp, ci, ci, vp, ll, ll, ci, ci, C.POINTER(GribOpts), vp, vp, vp]
+    for name in EXPORTS_GRIBIN:
+        getattr(lib, name).restype = C.c_int
+        getattr(lib, name).argtypes = [vp, ci, ci, vp, ll, ci, ci, ci, C.POINTER(GribOpts), vp, vp]
     _lib = lib
     return lib
 

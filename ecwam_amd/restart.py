@@ -67,3 +67,39 @@ def read_fl(path: str, n: int, nang: int, nfre: int, dtype, record: int = 0) -> 
                 a = np.frombuffer(b"".join(chunks), dtype=dt).reshape(nfre, nang, n)
                 return np.ascontiguousarray(np.transpose(a, (2, 1, 0)))
     raise AssertionError("unreachable")
+
+
+def read_record(path: str, record: int = 0, dtype=np.uint8) -> np.ndarray:
+    """The payload of record number `record` (0-based) as the file holds it, flat and not transposed: the elements of
+    ``(((FL(IJ,K,M),IJ),K),M)`` in file order when viewed in the working precision (`dtype`), i.e. NANG * NFRE field vectors of n reals
+    each -- what ecwam_hip_getspec_unpack takes (Wamintgr.read_restart_device).  The record markers are read as in read_fl: sub-records are
+    joined, the markers checked."""
+    with open(path, "rb") as f:
+        # first pass over the markers: where the sub-records of the wanted record lie
+        for rec in range(record + 1):
+            parts, total = [], 0
+            while True:
+                h = f.read(4)
+                if len(h) != 4:
+                    raise EOFError(f"{path}: record {rec} not found")
+                head = int(np.frombuffer(h, "<i4")[0])
+                ln = abs(head)
+                parts.append((f.tell(), ln))
+                f.seek(ln, 1)
+                total += ln
+                t = f.read(4)
+                if len(t) != 4 or abs(int(np.frombuffer(t, "<i4")[0])) != ln:
+                    raise ValueError(f"{path}: corrupt record markers ({head} / {t!r})")
+                if head >= 0:  # last (or only) sub-record
+                    break
+        dt = np.dtype(dtype)
+        if total % dt.itemsize:
+            raise ValueError(f"{path}: record holds {total} bytes, no whole number of {dt}")
+        raw = np.empty(total, np.uint8)
+        off = 0
+        for pos, ln in parts:
+            f.seek(pos)
+            if f.readinto(memoryview(raw)[off:off + ln]) != ln:
+                raise EOFError(f"{path}: record {record} is cut short")
+            off += ln
+    return raw.view(dt)

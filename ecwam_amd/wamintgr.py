@@ -597,6 +597,40 @@ class Wamintgr:
         self.fl1[: self.n] = torch.from_numpy(a).to(self.dev)
         self.gfast_valid = False
 
+    def read_restart_device(self, path: str) -> None:
+        """read_restart without a transposition on the host: the record goes to the device as the file holds it (NANG * NFRE field vectors
+        of n reals, staged in the storage of FL3) and ecwam_hip_getspec_unpack turns it into FL1's rows.  The same bits as read_restart."""
+        from . import restart
+        nf = self.cfg.nang * self.cfg.nfre
+        rec = restart.read_record(path, dtype=self.npdt)
+        if rec.size != self.n * nf:
+            raise ValueError(f"{path}: record holds {rec.size} reals, expected {self.n * nf} for FL({self.n},{self.cfg.nang},{self.cfg.nfre})")
+        if self.n:
+            blk = self.fl3.view(-1)[: rec.size].view(nf, self.n)
+            blk.copy_(torch.from_numpy(rec).view(nf, self.n))
+            self.ctx.getspec_unpack(0, self.n, blk, self.fl1)
+        self.gfast_valid = False
+
+    def getspec(self, values, fields=None, unscale: bool = True, nfre_red: int | None = None, opts=None) -> None:
+        """GETSPEC's GRIB read on one task (getspec.F90:396-660) from decoded vectors: values is one slab [nfld][NTENCODE] of the fields
+        (ifld0, nfld) -- default: from field 0 -- or an iterable of slabs (ifld0, array); arrays on the host are uploaded as they are.  Every
+        slab goes through the map of set_grib_map into FL1 (un-scaled unless unscale is off, ZMISS -> EPSMIN); after the last one the tail
+        above nfre_red (default NFRE_RED) is filled and SDEPTHLIM applied (getspec_tail)."""
+        if getattr(self, "ntencode", None) is None:
+            raise RuntimeError("getspec: set_grib_map() first")
+        if isinstance(values, (np.ndarray, torch.Tensor)):
+            if fields is not None and int(fields[1]) != values.shape[0]:
+                raise ValueError("getspec: the slab does not hold the fields named")
+            values = [(0 if fields is None else int(fields[0]), values)]
+        elif fields is not None:
+            raise ValueError("getspec: every slab of an iterable names its own first field")
+        for ifld0, a in values:
+            if isinstance(a, np.ndarray):
+                a = torch.from_numpy(np.ascontiguousarray(a, dtype=self.npdt))
+            self.ctx.getspec_values(0, self.n, a.to(self.dev), self.fl1, int(ifld0), unscale, True, opts)
+        self.ctx.getspec_tail(0, self.n, self.fl1, self.ff, nfre_red)
+        self.gfast_valid = False
+
     # ---- the start spectra on the device-resident FL1 and FF, over the local rows (csrc/start.hip): a run that does not begin from a restart file
     def delphi(self) -> float:
         """DELPHI, the latitude increment in metres (readmdlconf.F90:136: XDELLA CIRC / 360)"""
