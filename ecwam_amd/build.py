@@ -46,6 +46,10 @@ VARIANTS = {"": FAST_DIV, "exactdiv": ["-DECWAM_HIP_STRICT=0"], "strict1": ["-DE
             # SINPUT's leading rows without growth through the row loop like every other row (implsch_v4.h::v4_sinput): bit-identical to the
             # product, which takes them out in front of the loop (tests/test_gpu_sinput_lead.py), and the other side of an A/B in one tree
             "nolead": FAST_DIV + ["-DV4_SINPUT_LEAD=0"],
+            # the code a wave runs once as it was before it was trimmed (implsch_v4.h::V4_ONCE_TRIM: WSIGSTAR's three powers one after the
+            # other, XLLWS by 64-bit compares, DFIM / SQRT(WAVNUM) on every lane of every row, SETICE's rows on every wave): bit-identical to the
+            # product (tests/test_gpu_once_per_wave.py), and the other side of an A/B in one tree
+            "notrim": FAST_DIV + ["-DV4_ONCE_TRIM=0"],
             # the one-kernel builds at -O1 (with every double precision direction count enabled in implsch4a.hip this was the proof that their -O3
             # failures are code generation: profiles/r06_fused_step_experiments.txt)
             "advO1": FAST_DIV + ["-O1"]}

@@ -68,12 +68,19 @@ __device__ void taut_z0_c(const DevTab<T>& tb, int IUSFG, T UTOP, T COSDIFF, T T
   CHRNCK = m_max(tb.G * Z0 * USTM1 * USTM1, tb.ALPHAMIN);
 }
 
-// wsigstar.F90:87-129
+// wsigstar.F90:87-129.  The free-convection factor (0.5 XKAPPA WSTAR**3)**(1/3) depends on the forcing alone: wsigstar_w3rt; the rest, given
+// that factor: wsigstar_r (k_implsch4_pre evaluates the factor one sea point per lane and hands it to k_implsch4, whose scalar stage has
+// a few lanes at work: one expansion of the power function less there).  The same function on the same argument: the same bits.
 template <typename T>
-__device__ T wsigstar(const DevTab<T>& tb, T WSWAVE, T UFRIC, T Z0M, T WSTAR) {
-  const T ONETHIRD = T(1) / T(3), SIG_NMAX = T(0.9);
-  const T C1 = T(1.03E-3), C2 = T(0.04E-3), P1 = T(1.48), P2 = T(-0.21);
+__device__ __forceinline__ T wsigstar_w3rt(const DevTab<T>& tb, T WSTAR) {
+  const T ONETHIRD = T(1) / T(3);
   const T w3 = T(0.5) * tb.XKAPPA * (WSTAR * WSTAR * WSTAR);  // BG_GUST = 0
+  return m_pow(T(0) + w3, ONETHIRD);
+}
+template <typename T>
+__device__ T wsigstar_r(const DevTab<T>& tb, T WSWAVE, T UFRIC, T Z0M, T W3RT) {
+  const T SIG_NMAX = T(0.9);
+  const T C1 = T(1.03E-3), C2 = T(0.04E-3), P1 = T(1.48), P2 = T(-0.21);
   if (tb.LLGCBZ0 || tb.LLNORMAGAM) {
     T U10M1 = T(1) / m_max(WSWAVE, tb.WSPMIN);
     T Z0VIS = tb.RNUM / m_max(UFRIC, tb.EPSUS);
@@ -82,7 +89,7 @@ __device__ T wsigstar(const DevTab<T>& tb, T WSWAVE, T UFRIC, T Z0M, T WSTAR) {
     T BCD_LOC = tb.BCDLIN * m_sqrt(ZCHAR);
     T C_D = tb.ACDLIN + BCD_LOC * WSWAVE;
     T SIG_CONV = T(1) + T(0.5) * WSWAVE / C_D * BCD_LOC;
-    return m_min(SIG_NMAX, SIG_CONV * U10M1 * m_pow(T(0) + w3, ONETHIRD));
+    return m_min(SIG_NMAX, SIG_CONV * U10M1 * W3RT);
   }
   T U10 = UFRIC * (T(1) / tb.XKAPPA) * (m_log(T(10)) - m_log(Z0M));
   U10 = m_max(U10, tb.WSPMIN);
@@ -92,6 +99,10 @@ __device__ T wsigstar(const DevTab<T>& tb, T WSWAVE, T UFRIC, T Z0M, T WSTAR) {
   T C_D = (C1 + C2U10P1) * U10P2;
   T DC_DDU = (P2 * C1 + (P1 + P2) * C2U10P1) * U10P2 * U10M1;
   T SIG_CONV = T(1) + T(0.5) * U10 / C_D * DC_DDU;
-  return m_min(SIG_NMAX, SIG_CONV * U10M1 * m_pow(T(0) + w3, ONETHIRD));
+  return m_min(SIG_NMAX, SIG_CONV * U10M1 * W3RT);
+}
+template <typename T>
+__device__ T wsigstar(const DevTab<T>& tb, T WSWAVE, T UFRIC, T Z0M, T WSTAR) {
+  return wsigstar_r(tb, WSWAVE, UFRIC, Z0M, wsigstar_w3rt(tb, WSTAR));
 }
 

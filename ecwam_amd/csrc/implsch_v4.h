@@ -47,6 +47,14 @@
 #ifndef V4_SINPUT_LEAD
 #define V4_SINPUT_LEAD 1
 #endif
+// The code a wave runs once, trimmed (every item bit-identical by construction): WSIGSTAR's free-convection power not here but as a
+// factor k_implsch4_pre hands in (implsch_common.h::wsigstar_r) and, in single precision, XLLWS from the 32-bit halves of the masks, FKMEAN's
+// DFIM / SQRT(WAVNUM) once per (point, M) in the factor table instead of on every lane of every row, SETICE's row loop skipped on waves without
+// an ice point (in double precision each of the three costs AGPR copies in some build: as they were); 0 = the build variant "notrim", the
+// code as it was: the bit-identity partner of tests/test_gpu_once_per_wave.py and the other side of an A/B
+#ifndef V4_ONCE_TRIM
+#define V4_ONCE_TRIM 1
+#endif
 #define V4_NSTG 4
 // frequencies per lane: lane j of a point owns M = q G + j + 1, q = 0 .. NS - 1 (36 directions: 2, 24: 3, 12: 6; 48 directions: 2 with the
 // second one only on the lanes j < NFRE - G = 12 -- the other lanes repeat frequency NFRE: the same stores, a weight of zero in the sums)
@@ -63,7 +71,8 @@ using V2 = T __attribute__((ext_vector_type(2)));
 // the row of scalars per sea point that k_implsch4_pre hands to k_implsch4 and k_implsch4 to k_implsch4_fin
 enum { FIN_AIRD = 0, FIN_UFRIC, FIN_Z0M, FIN_MIJ, FIN_XS, FIN_YS, FIN_F1DCOS3, FIN_F1DCOS2, FIN_F1DSIN2, FIN_F1D, FIN_RNFAC, FIN_PHIWA,
        FIN_SINWD, FIN_COSWD, FIN_WSWAVE, FIN_CICOVER, FIN_PHILF, FIN_XSTRESS, FIN_YSTRESS, FIN_Z0B, FIN_CHRNCK, FIN_COSDIFF, FIN_EMEAN, FIN_F1MEAN,
-       FIN_TAUICX, FIN_TAUICY, FIN_STRNMS, FIN_SPARE,                   // (these four: the RARE build's ice stress and strain)
+       FIN_TAUICX, FIN_TAUICY, FIN_STRNMS,                              // (these three: the RARE build's ice stress and strain)
+       FIN_W3RT,                                                        // WSIGSTAR's free-convection factor, from k_implsch4_pre (V4_ONCE_TRIM)
        // the two-kernel split (PART = 1 -> PART = 2): means of the spectrum before the update, the windsea mean frequency of the second
        // SINFLX call, SDIWBK's rate and the scale of SDEPTHLIM (the second kernel re-applies it to the spectrum it loads)
        FIN_FMEAN, FIN_FMEANWS, FIN_AKMEAN, FIN_XKMEAN, FIN_SDS, FIN_SC, V4_NFIN = 36 };
@@ -1493,6 +1502,9 @@ k_implsch4(const DevTab<T>* __restrict__ tp, int kijs, int kijl, T* __restrict__
   const T p_emaxdpt = ffp[14], p_depth = ffp[15];
   const T p_sinwd = frp[FIN_SINWD], p_coswd = frp[FIN_COSWD], p_rnfac = frp[FIN_RNFAC], p_cosdiff = frp[FIN_COSDIFF];
   const T p_ufric = frp[FIN_UFRIC], p_z0m = frp[FIN_Z0M], p_z0b = frp[FIN_Z0B], p_chrnck = frp[FIN_CHRNCK];
+#if V4_ONCE_TRIM
+  const T p_w3rt = frp[FIN_W3RT];
+#endif
   T h_o[PART == 2 ? 9 : 1];   // PART 2: what PART 1 handed over (loaded with the rest, unconditionally)
   if constexpr (PART == 2) {
     h_o[0] = frp[FIN_MIJ]; h_o[1] = frp[FIN_SDS]; h_o[2] = frp[FIN_EMEAN]; h_o[3] = frp[FIN_F1MEAN]; h_o[4] = frp[FIN_FMEAN];
@@ -1517,6 +1529,9 @@ k_implsch4(const DevTab<T>* __restrict__ tp, int kijs, int kijl, T* __restrict__
     if (EXT && tb.LLGCBZ0) q[C_TWCOS] = p_cosdiff;
     q[C_UFRIC] = p_ufric; q[C_Z0M] = p_z0m; q[C_Z0B] = p_z0b; q[C_CHRNCK] = p_chrnck;
     q[C_SPARE] = p_ci;   // CICOVER
+#if V4_ONCE_TRIM
+    q[C_SIGN] = p_w3rt;  // WSIGSTAR's free-convection factor until WSIGSTAR puts SIG_N there (the first SINFLX call has no gustiness)
+#endif
     if constexpr (PART == 2) {
       q[C_MIJ] = h_o[0]; q[C_SDS] = h_o[1]; q[C_EMEAN] = h_o[2]; q[C_F1MEAN] = h_o[3];
       q[C2_FMEAN] = h_o[4]; q[C2_FMEANWS] = h_o[5]; q[C2_AKMEAN] = h_o[6]; q[C2_XKMEAN] = h_o[7]; q[C2_SC] = h_o[8];
@@ -1566,6 +1581,12 @@ k_implsch4(const DevTab<T>* __restrict__ tp, int kijs, int kijl, T* __restrict__
       T* f = L.fac4 + m * 4;
       const T WAVNUM = w_wn[qq], XK2CG = w_xk[qq];
       f[Q4_WAVNUM] = WAVNUM; f[Q4_CINV] = w_ci[qq]; f[Q4_BSC] = WAVNUM * (T(1) / tb.ZPI) * XK2CG; L.sq[m] = m_sqrt(WAVNUM);
+#if V4_ONCE_TRIM
+      // DFIM(M) / SQRT(WAVNUM) of FKMEAN's mean wavenumber, once per (point, M): the LOG plane is free until SINPUT fills it (lane M - 1
+      // holds DFIM(M): one exchange; the quotient is the expression of the row loop on the same two values).  Single precision: in double
+      // precision the row loop without its quotient is unrolled further and takes two more AGPR copies.
+      if constexpr (PART != 2 && RLANE) L.zcn[m] = fs_div<32>(v4_bp(4 * m, L.rDFIM), m_sqrt(WAVNUM));
+#endif
       T sbo = T(0);   // sbottom.F90:79-89
       if (m < tb.NFRE_RED && DEPTHv < tb.BATHYMAX) sbo = (-T(2) * T(0.038) * tb.GM1) * WAVNUM / m_sinh(m_min(T(2) * DEPTHv * WAVNUM, T(50)));
       if (ice1 || ice3) {
@@ -1674,7 +1695,12 @@ k_implsch4(const DevTab<T>* __restrict__ tp, int kijs, int kijl, T* __restrict__
       const T* row = tb.SINROW[m];
       const T dfm = RLANE ? lane_get(L.rDFIM, m) : row[1], sqm = L.sq[m], sig = RLANE ? lane_get(L.rZPIFR, m) : row[0];
       s0 = s0 + V2<T>{dfm, RLANE ? lane_get(L.rDFIMOFR, m) : row[5]} * t;
-      s1 = s1 + V2<T>{RLANE ? lane_get(L.rDFIMFR, m) : row[6], fs_div<32>(dfm, sqm)} * t;
+#if V4_ONCE_TRIM
+      const T dosq = RLANE ? L.zcn[m] : fs_div<32>(dfm, sqm);      // single precision: DFIM(M) / SQRT(WAVNUM) from the factor table's fill
+#else
+      const T dosq = fs_div<32>(dfm, sqm);
+#endif
+      s1 = s1 + V2<T>{RLANE ? lane_get(L.rDFIMFR, m) : row[6], dosq} * t;
       s2.x = s2.x + (sqm * dfm) * t;
       if (last) {
         s2.y = t;
@@ -1722,7 +1748,11 @@ k_implsch4(const DevTab<T>* __restrict__ tp, int kijs, int kijl, T* __restrict__
       const T WSW = cq[C_WSWAVE], WST = cq[C_WSTAR];
       taut_z0_b_rows(tb, lane & 15, iusfg, cq[C_HALP], WSW, cosd, cq[C_TAUW], cq[C_RNFAC], UF, Z0, Z0Bv, CH);
       T sgn = T(0);
+#if V4_ONCE_TRIM
+      if (iusfg) sgn = wsigstar_r(tb, WSW, UF, Z0, cq[C_SIGN]);   // (the slot holds k_implsch4_pre's free-convection factor)
+#else
       if (iusfg) sgn = wsigstar(tb, WSW, UF, Z0, WST);
+#endif
       WSYNC();
       if ((lane & 15) == 0) {
         cq[C_UFRIC] = UF; cq[C_Z0M] = Z0; cq[C_Z0B] = Z0Bv; cq[C_CHRNCK] = CH;
@@ -1842,7 +1872,11 @@ k_implsch4(const DevTab<T>* __restrict__ tp, int kijs, int kijl, T* __restrict__
     // WSIGSTAR and the swell set-up, on UFRIC / Z0M as they came
     if (lane < PP) {
       T* q = sSC + lane * NSC;
+#if V4_ONCE_TRIM
+      q[C_SIGN] = wsigstar_r(tb, q[C_WSWAVE], q[C_UFRIC], q[C_Z0M], q[C_SIGN]);   // (the slot holds k_implsch4_pre's free-convection factor)
+#else
       q[C_SIGN] = wsigstar(tb, q[C_WSWAVE], q[C_UFRIC], q[C_Z0M], q[C_WSTAR]);
+#endif
       swell_setup_pt(tb, q);
     }
     WSYNC();
@@ -1878,7 +1912,11 @@ k_implsch4(const DevTab<T>* __restrict__ tp, int kijs, int kijl, T* __restrict__
       T UF = q[C_UFRIC], Z0 = q[C_Z0M], Z0Bv = q[C_Z0B], CH = q[C_CHRNCK];
       taut_z0_c(tb, 1, q[C_WSWAVE], q[C_COSWD] * q[C_TWCOS] + q[C_SINWD] * q[C_TWSIN], q[C_TAUW], UF, Z0, Z0Bv, CH);
       q[C_UFRIC] = UF; q[C_Z0M] = Z0; q[C_Z0B] = Z0Bv; q[C_CHRNCK] = CH;
+#if V4_ONCE_TRIM
+      q[C_SIGN] = wsigstar_r(tb, q[C_WSWAVE], UF, Z0, q[C_SIGN]);   // (the slot holds k_implsch4_pre's free-convection factor)
+#else
       q[C_SIGN] = wsigstar(tb, q[C_WSWAVE], UF, Z0, q[C_WSTAR]);
+#endif
     }
     swell_setup_pt(tb, q);
     q[C_SDS] = sdiwbk_pt(tb, q[C_EMAXDPT], q[C_EMEAN], q[C_F1MEAN], q[C_DEPTH]);
@@ -1920,11 +1958,20 @@ k_implsch4(const DevTab<T>* __restrict__ tp, int kijs, int kijl, T* __restrict__
 #pragma unroll 1
     for (int h = 0; h < 2; h++) {
       const unsigned long long xm = h ? xm1 : xm0;
+#if V4_ONCE_TRIM
+      // single precision: a bit-field extract and a conversion per element, exactly 0.0 / 1.0 (double precision: two more AGPR copies in
+      // the WDFLUXES build at 12 directions, so as it was)
+      const unsigned xh[2] = {(unsigned)xm, (unsigned)(xm >> 32)};
+#endif
 #pragma unroll
       for (int m = 0; m < NFRE; m += VEC) {
         VT val;
 #pragma unroll
+#if V4_ONCE_TRIM
+        for (int i = 0; i < VEC; i++) val[i] = RLANE ? (T)((xh[(m + i) >> 5] >> ((m + i) & 31)) & 1u) : (((xm >> (m + i)) & 1ull) ? T(1) : T(0));
+#else
         for (int i = 0; i < VEC; i++) val[i] = ((xm >> (m + i)) & 1ull) ? T(1) : T(0);
+#endif
         *reinterpret_cast<VT*>(x0 + h * NFRE + m) = val;
       }
     }
@@ -2499,7 +2546,18 @@ k_implsch4(const DevTab<T>* __restrict__ tp, int kijs, int kijl, T* __restrict__
       *reinterpret_cast<V2<T>*>(tFw + m * RS) = V2<T>{m_max(tm * tf.x, FLM.x), m_max(tm * tf.y, FLM.y)};
     }
   }
-  if (!WDF && tb.LICERUN && tb.LMASKICE) {  // setice.F90:67-86 (OUTSTEP0 calls it on its own: k_setice)
+#if V4_ONCE_TRIM
+  // A wave with no point above CITHRSH (one ballot) skips the rows: what it would do to them is F * 1 + (0 * FLMIN) cos^2 = F + (+0), which
+  // changes a bit only where F is -0 (-0 + +0 = +0), and no row holds a -0 here: every row m is the sweep's MIN(MAX(., FLM), FLMAX) (m < the
+  // highest cut-off of the wave) or IMPHFTAIL's MAX(., FLM) (m >= the point's cut-off, which is not above the wave's highest), FLM is +0
+  // or positive, and the maximum of -0 and +0 is +0 (v_max_f32 / v_pk_max_f32 / v_max_f64 order the zeros) -- nor does a -0 come up in
+  // the first place other than from a -0 in the caller's spectrum: F + (-F) = +0, and the tail is a product of values that are not negative.
+  // (Single precision: in double precision the branch takes two more AGPR copies in the alternate build at 48 directions.)
+  const bool ice_rows = !RLANE || __builtin_amdgcn_ballot_w64(CICOVER > tb.CITHRSH) != 0ull;
+#else
+  const bool ice_rows = true;
+#endif
+  if (!WDF && tb.LICERUN && tb.LMASKICE && ice_rows) {  // setice.F90:67-86 (OUTSTEP0 calls it on its own: k_setice)
     T CIREDUC, ICEFREE;
     if (CICOVER > tb.CITHRSH) { CIREDUC = m_max(tb.EPSMIN, T(1) - CICOVER); ICEFREE = T(0); }
     else { CIREDUC = T(0); ICEFREE = T(1); }
@@ -2620,6 +2678,9 @@ __global__ void __launch_bounds__(64) k_implsch4_pre(const DevTab<T>* __restrict
   T RNFAC = T(1);   // sinflx.F90:116-120
   if (EXT && tb.LLNORMAGAM && tb.LLCAPCHNK) RNFAC = T(1) + tb.DTHRN_A * (T(1) + m_tanh(WSWAVE - tb.DTHRN_U));
   fr[FIN_RNFAC] = RNFAC;
+#if V4_ONCE_TRIM
+  fr[FIN_W3RT] = wsigstar_w3rt(tb, ff[4]);      // (0.5 XKAPPA WSTAR**3)**(1/3): the forcing's alone, so not on the few lanes of k_implsch4's scalar stage
+#endif
   T UFRIC = ff[7], Z0M = ff[10], Z0B = ff[11], CHRNCK = ff[12];
   if (!WDF && EXT && tb.LLGCBZ0) fr[FIN_COSDIFF] = m_cos(WDWAVE - ff[9]);
   if (WDF) {      // (nothing more: the scalars below go through as they came)
