@@ -46,6 +46,9 @@ VARIANTS = {"": FAST_DIV, "exactdiv": ["-DECWAM_HIP_STRICT=0"], "strict1": ["-DE
             # SINPUT's leading rows without growth through the row loop like every other row (implsch_v4.h::v4_sinput): bit-identical to the
             # product, which takes them out in front of the loop (tests/test_gpu_sinput_lead.py), and the other side of an A/B in one tree
             "nolead": FAST_DIV + ["-DV4_SINPUT_LEAD=0"],
+            # the length of that run found row by row, one ballot and branch per row (implsch_v4.h::V4_SINPUT_PAR): bit-identical to the product,
+            # which finds it in one lane-parallel pass (tests/test_gpu_sinput_par.py), and the other side of an A/B in one tree
+            "nopar": FAST_DIV + ["-DV4_SINPUT_PAR=0"],
             # the code a wave runs once as it was before it was trimmed (implsch_v4.h::V4_ONCE_TRIM: WSIGSTAR's three powers one after the
             # other, XLLWS by 64-bit compares, DFIM / SQRT(WAVNUM) on every lane of every row, SETICE's rows on every wave): bit-identical to the
             # product (tests/test_gpu_once_per_wave.py), and the other side of an A/B in one tree

@@ -47,6 +47,12 @@
 #ifndef V4_SINPUT_LEAD
 #define V4_SINPUT_LEAD 1
 #endif
+// The length of that run from one lane-parallel pass (the minimum of 1 / COSLP over the point's directions, then one test per (point, row))
+// instead of one ballot and branch per row (single precision, v4_sinput); 0 = the build variant "nopar", the row-by-row test: the
+// bit-identity partner of tests/test_gpu_sinput_par.py and the other side of an A/B
+#ifndef V4_SINPUT_PAR
+#define V4_SINPUT_PAR 1
+#endif
 // The code a wave runs once, trimmed (every item bit-identical by construction): WSIGSTAR's free-convection power not here but as a
 // factor k_implsch4_pre hands in (implsch_common.h::wsigstar_r) and, in single precision, XLLWS from the 32-bit halves of the masks, FKMEAN's
 // DFIM / SQRT(WAVNUM) once per (point, M) in the factor table instead of on every lane of every row, SETICE's row loop skipped on waves without
@@ -233,6 +239,40 @@ __device__ __forceinline__ T v4_allmax1(T v, const V4Rot<T>& r) {
     if (G == 24) v = m_max(v, v4_bp(r.a2, v));
     return m_max(v, m_max(v4_bp(r.a3, v), v4_bp(r.a4, v)));
   }
+}
+
+// minimum over the lanes of a point (SINPUT's run of rows without growth: the smallest 1 / COSLP; single precision), v4_allmax1's exchanges
+template <int G>
+__device__ __forceinline__ float v4_allmin1(float v, const V4Rot<float>& r) {
+  if constexpr (G == 18) {
+    v = m_min(v, v4_bp(r.a0, v));
+    asm volatile("s_nop 1\n\tv_min_f32_dpp %0, %0, %0 row_ror:8 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+                 "s_nop 1\n\tv_min_f32_dpp %0, %0, %0 row_ror:4 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+                 "s_nop 1\n\tv_min_f32_dpp %0, %0, %0 row_ror:2 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+                 "s_nop 1\n\tv_min_f32_dpp %0, %0, %0 row_ror:1 row_mask:0xf bank_mask:0xf bound_ctrl:1"
+                 : "+v"(v));
+    return v4_bp(r.a1, v);
+  } else {
+    v = m_min(v, v4_bp(r.a0, v));
+    if (G >= 12) v = m_min(v, v4_bp(r.a1, v));
+    if (G == 24) v = m_min(v, v4_bp(r.a2, v));
+    return m_min(v, m_min(v4_bp(r.a3, v), v4_bp(r.a4, v)));
+  }
+}
+// the lowest j of the point-lanes set in a ballot (lane -> (point, j) as k_implsch4 lays a wave out; spare lanes are not looked at: each
+// shadows a real lane), -1: none.  Scalar code on the ballot's 64 bits.
+template <int G, int PP>
+__device__ __forceinline__ int v4_first_j(unsigned long long mask) {
+  unsigned f = 0u;
+  if constexpr (G == 18) {
+    const unsigned e = (unsigned)(mask >> 48) & 0x3fu;      // lanes 48 .. 53: j = 16, 17 of the points 0, 1, 2
+    f = (((unsigned)mask | (unsigned)(mask >> 16) | (unsigned)(mask >> 32)) & 0xffffu) | (((e | (e >> 2) | (e >> 4)) & 3u) << 16);
+  } else {
+    static_assert(PP * G <= 64, "one wave");
+#pragma unroll
+    for (int q = 0; q < PP; q++) f |= (unsigned)(mask >> (q * G)) & ((1u << G) - 1u);
+  }
+  return f ? __builtin_ctz(f) : -1;
 }
 
 // UNI (the WDFLUXES builds): the value of the point's lane j = 0 on every lane of the point.  With 48 / 24 / 12 directions the all-reduce leaves
@@ -786,7 +826,7 @@ __device__ void v4_sinput(const DevTab<T>& tb, const V4Ctx<T, NANG, PP>& L, T UF
   // GAM0 = 0 on every lane and in both gust states.  While XSTRESS = YSTRESS = +0 the chain of a row (sheltered stress, its direction,
   // U*, COSLP and its reciprocals) does not depend on the row: it is evaluated once, with the expressions of the row loop below.  Then
   // 1. the length m0 of the run (wave-uniform, 0 .. NFRE): per row U*/c, the two ZLOG per gust state and ONE ballot over "some lane
-  //    grows"; the first row with a lane that grows ends it;
+  //    grows"; the first row with a lane that grows ends it (V4_SINPUT_PAR, the product: the same row from one test per (point, row), below);
   // 2. what a row of the run owes, i.e. what does not vanish: zero row integrals, and in the second call the damping DSTAB -> FLP, the
   //    coefficient store, APL and a zero row total;
   // 3. the row loop below starts at m0 and runs every row from there on as it always did, with XSTRESS = YSTRESS = +0 at its first row
@@ -824,8 +864,60 @@ __device__ void v4_sinput(const DevTab<T>& tb, const V4Ctx<T, NANG, PP>& L, T UF
       rcl[ig] = V2<T>{fs_rcp<4>(coslp.x), fs_rcp<4>(coslp.y)};
       ds2[ig] = LLSNEG ? TEMP2 + (FU + FUD * coslp) * USTPg : z2;
     }
-    // 1. the length of the run: nothing but the test, the next row's CINV and LOG(WAVNUM Z0M) read ahead of it
-    {
+    // 1. the length of the run.
+    // V4_SINPUT_PAR (single precision): in ONE pass over the lanes instead of row by row.  Inside the run the chain above is the chain of every
+    // row, so of the row test Z = ZCN(m) + UCNZALPD(m) / COSLP only ZCN and UCNZALPD = XKAPPA / (U*/c(m) + ZALP) depend on the row, and they
+    // belong to (point, row), not to a direction.  UCNZALPD >= 0 (XKAPPA > 0 times a hardware reciprocal of U* CINV + ZALP > 0), and for such a
+    // factor the test's Z = fma(UCNZALPD, r, ZCN) -- one rounding of a non-decreasing function of r; the same holds for a rounded product plus
+    // a rounded sum -- is a non-decreasing function of r = 1 / COSLP: rounding is monotone.  Hence, with rmin the minimum of the lanes'
+    // very rcl values over the directions of the point that pass COSLP > 0.01 (+infinity when none does):
+    //     some passing direction of the point has Z < 0   <=>   fma(UCNZALPD, rmin, ZCN) < 0
+    // (<=: rmin is the rcl of a passing direction; =>: that direction's rcl >= rmin, so Z(rmin) <= its Z < 0.  None passing: Z(+infinity) is
+    // +infinity, or NaN for UCNZALPD = 0: not below zero.)  So: one minimum all-reduce of rcl per gust state over the point's lanes (exact),
+    // then lane j of the point tests the rows j, j + G, ... of ITS OWN point -- all PP NFRE (point, row) pairs in NFRE / G passes (36
+    // directions: two), the chain's U* and rmin already in the lane, ZCN and CINV read at the lane's own row, no exchange --, one ballot per
+    // pass, and m0 is the lowest row set over the passes: the row at which the row-by-row test below stops.  The row's expression is that
+    // test's own, operand for operand, with its two multiply-adds -- U* CINV + ZALP and Z -- SPELT OUT as fused ones.  The row-by-row test
+    // below leaves them to the compiler's contraction, which fuses both there in both calls (v_fma_f32 / v_fmac_f32 in the ISA:
+    // profiles/r10_sinput_par_isa.txt): the one-pass test and the row-by-row test are the same arithmetic.  Left to contraction here, one of
+    // the two passes of the second call at 36 directions got v_pk_mul_f32 + v_add_f32 for Z (the two gust states' tests had become one MIN),
+    // a rounded product where the row-by-row test has none.  Likewise rmin reaches the test as a positive minimum: as -MAX(-rcl) the compiler
+    // turns ZCN - UCNZALPD MAX < 0 into ZCN < UCNZALPD MAX, a rounded product again.
+    // Against the ROW LOOP there is one difference, and it is V4_SINPUT_LEAD's, not this switch's: in the row loop of the FIRST call (NGST = 1)
+    // the product U* CINV has a second use (Z2X) and is NOT fused into the sum -- v_pk_mul_f32, then v_add_f32 with ZALP -- while both forms of
+    // the run's test fuse it; Z is fused everywhere, and so is U* CINV + ZALP in the second call's row loop (v_pk_fma_f32).  The first call's
+    // run therefore ends where a denominator that may differ from the row loop's by one rounding says: at a row whose Z is within about an
+    // ulp of ZCN of zero (of the order of 1e-6 of a row's step in Z) the run can take in a row that the row loop would have found to grow in
+    // one direction -- that row then loses its XLLWS bit and a growth term of the size of Z**4 -- or stop a row early, which changes nothing.
+    // "nolead" and the product are the same bits wherever no row is that close; the tests have met no such row.
+    // The diagnostic builds with ECWAM_HIP_STRICT != 0 keep the row-by-row test ("strict7" compiles with contraction off: its row loop's Z
+    // is a product and a sum, and the run must end where the row loop's own test says).
+    if constexpr ((V4_SINPUT_PAR != 0) && sizeof(T) == 4 && ECWAM_HIP_STRICT == 0) {
+      T rmin[NGST];
+#pragma unroll
+      for (int ig = 0; ig < NGST; ig++) {
+        const T PINF = __builtin_huge_valf();
+        rmin[ig] = v4_allmin1<G>(m_min(c0[ig] ? rcl[ig].x : PINF, c1[ig] ? rcl[ig].y : PINF), L.rot);
+      }
+      m0 = NFRE;
+#pragma unroll
+      for (int s = NS - 1; s >= 0; s--) {
+        const int mr = s * G + L.j;
+        const bool in = (NS * G == NFRE) || mr < NFRE;      // (48 directions: the lanes j >= NFRE - G have no second row)
+        const int mi = in ? mr : NFRE - 1;
+        const T cinv_m = L.fac4[mi * 4 + Q4_CINV], ZCN = L.zcn[mi];
+        bool grows = false;
+#pragma unroll
+        for (int ig = 0; ig < NGST; ig++) {
+          const T den = __builtin_fmaf(ig ? vUSTP0.y : vUSTP0.x, cinv_m, ZALP);
+          const T UCNZALPD = XKAPPA * fs_rcp<8>(den);
+          const T Z = __builtin_fmaf(UCNZALPD, rmin[ig], ZCN);
+          grows = grows || (Z < T(0));
+        }
+        const int jf = v4_first_j<G, PP>(__builtin_amdgcn_ballot_w64(grows && in));
+        m0 = jf >= 0 ? s * G + jf : m0;      // (the passes from the last to the first: the lowest one that has a row stays)
+      }
+    } else {
       T ci_n = L.fac4[Q4_CINV], zcn_l = L.zcn[0];
 #pragma unroll 1
       for (; m0 < NFRE; m0++) {
