@@ -16,6 +16,7 @@ from . import lib as _lib
 from .tables import Tables
 
 NFF, NINTF, NWPR = 16, 16, 5
+NFIELDG = len(_lib.FG_PLANES)      # the planes of fieldg (include/ecwam_hip_forcing.h)
 # columns of ecwam_hip_outbs_sepwisw (include/ecwam_hip.h): OUTBLOCK parameters 20-22, 11-16, 23-28
 OUTBS_SEP_FIELDS = ("mp1", "mp2", "wdw", "shww", "shts", "mdww", "mdts", "mpww", "mpts",
                     "p1sea", "p1swell", "p2sea", "p2swell", "sprdsea", "sprdswell")
@@ -461,6 +462,93 @@ class HipContext:
         ncell = getattr(self, "_fmap", (0, 0, 0))[2]
         self._chk(self.lib.ecwam_hip_fldtoifs(self._h, kijs, kijl, self._real(wvblock, (nwv, ld), "WVBLOCK"), ld, nwv,
                                               None if d is None else d.ctypes.data_as(C.c_void_p), self._real(grid, (nwv, ncell), "GRID"), _stream_ptr()))
+
+    # -- the forcing intake (include/ecwam_hip_intake.h; csrc/intake.hip): what PREWIND runs in front of GETWND, and the hand-over to NEMO
+    def set_fldinter(self, idx, w=None, ngptotg: int = 0, interpol: bool = True) -> None:
+        """The per-point table of FLDINTER (intake.point_table builds it): idx host integers [npts][4], the 0-based positions of the four corners
+        in a field vector; w host numbers [npts][3], DJ1M, DII1M, DIIP1M in the working precision; ngptotg the length of a field vector.
+        interpol=False is LLINTERPOL = F: only idx[:, 0] is read.  idx=None removes the table.  The library validates and uploads it; a later
+        set_forcing_map drops it."""
+        if idx is None:
+            self._chk(self.lib.ecwam_hip_set_fldinter(self._h, 0, 0, None, None, 0))
+            self._fli = None
+            return
+        a = np.ascontiguousarray(idx, dtype=np.int32)
+        if a.ndim != 2 or a.shape[1] != 4:
+            raise ValueError("set_fldinter: idx is [npts][4]")
+        pw = None
+        if w is not None:
+            pw = np.ascontiguousarray(w, dtype=np.float64)
+            if pw.shape != (a.shape[0], 3):
+                raise ValueError("set_fldinter: w is [npts][3]")
+            if not np.array_equal(pw.astype(self.t.dtype).astype(np.float64), pw):
+                raise ValueError("set_fldinter: the weights are not values of the working precision")
+        self._chk(self.lib.ecwam_hip_set_fldinter(self._h, a.shape[0], int(ngptotg), a.ctypes.data_as(C.c_void_p),
+                                                  None if pw is None else pw.ctypes.data_as(C.c_void_p), int(bool(interpol))))
+        self._fli = (a.shape[0], int(ngptotg))
+
+    def fldinter(self, kijs, kijl, fields, fieldg, laden: bool = False, lgust: bool = False, llkc: bool = False, lwcur: bool = False, newcurr: bool = False,
+                 roair: float = 1.225, wstar0: float = 0.0, pmiss: float = -999.0, mask_in=None, flags: int | None = None):
+        """FLDINTER (fldinter.F90:176-374) on rows [kijs, kijl): fields [nfields][ngptotg] -> the planes of fieldg [13][ncell_in] through the inbound
+        map.  newcurr is LLNEWCURR .AND. .NOT. LWNEMOCOUCUR.  mask_in: an int32 cuda tensor [ngptotg] in which every position read becomes 1 (never
+        cleared).  flags (the lib.FLI_* bits) overrides the five switches."""
+        if flags is None:
+            flags = (_lib.FLI_LADEN if laden else 0) | (_lib.FLI_LGUST if lgust else 0) | (_lib.FLI_LLKC if llkc else 0) | (_lib.FLI_LWCUR if lwcur else 0) | \
+                (_lib.FLI_NEWCURR if newcurr else 0)
+        if fields.dim() != 2:
+            raise ValueError("FIELDS: expected [nfields][ngptotg]")
+        nf, ng = fields.shape
+        self._chk(self.lib.ecwam_hip_fldinter(self._h, int(kijs), int(kijl), self._real(fields, (nf, ng), "FIELDS"), ng, nf, int(flags), float(roair), float(wstar0),
+                                              float(pmiss), self._fieldg(fieldg), None if mask_in is None else self._int(mask_in, (ng,), "MASK_IN"), _stream_ptr()))
+
+    def init_fieldg(self, fieldg, roair: float = 1.225, wstar0: float = 0.0):
+        """The LLINIALL branch of INIT_FIELDG (init_fieldg.F90:92-116) on fieldg [13][ncell]: zeros, WSWAVE = WSPMIN, AIRD = roair, WSTAR = wstar0."""
+        if fieldg.dim() != 2 or fieldg.shape[0] != len(_lib.FG_PLANES):
+            raise ValueError("FIELDG: expected [13][ncell]")
+        self._chk(self.lib.ecwam_hip_init_fieldg(self._h, self._real(fieldg, tuple(fieldg.shape), "FIELDG"), int(fieldg.shape[1]), float(roair), float(wstar0),
+                                                 _stream_ptr()))
+
+    def recvnemofields(self, kijs, kijl, nemo, ff=None, ucur=None, vcur=None, intf=None, fieldg=None, nemoibr=None, lrest: bool = False, linit: bool = False,
+                       lwcou: bool | None = None, lwnemocoucic: bool = False, lwnemocoucit: bool = False, lwnemocoucur: bool = False,
+                       lwnemocouibr: bool = False, flags: int | None = None):
+        """The point-wise branches of RECVNEMOFIELDS on rows [kijs, kijl): lrest fills nemo (float64 [4][kijl]: exactly kijl points a plane) and
+        nemoibr (float64 [kijl]) from ff, the currents and IBRMEM = intf[:, 15]; linit sets those from nemo / nemoibr, with lwcou only where
+        LKFR of fieldg <= 0.  lwcou defaults to LWCOU of the parameters.  flags (the lib.RNF_* bits) overrides the switches."""
+        if flags is None:
+            lwcou = self.t.cfg.lwcou if lwcou is None else lwcou
+            flags = sum(b for b, on in ((_lib.RNF_LREST, lrest), (_lib.RNF_LINIT, linit), (_lib.RNF_LWCOU, lwcou), (_lib.RNF_LWNEMOCOUCIC, lwnemocoucic),
+                                        (_lib.RNF_LWNEMOCOUCIT, lwnemocoucit), (_lib.RNF_LWNEMOCOUCUR, lwnemocoucur), (_lib.RNF_LWNEMOCOUIBR, lwnemocouibr)) if on)
+        self._seam("RECVNEMOFIELDS", kijs, kijl, *[a for a in (ff, ucur, vcur, intf) if a is not None])
+
+        def dbl(a, shape, name):
+            if a is None:
+                return None
+            if not (a.is_cuda and a.dtype == torch.float64 and a.is_contiguous() and tuple(a.shape) == shape):
+                raise ValueError(f"{name}: expected a contiguous float64 cuda tensor of shape {shape}")
+            return a.data_ptr()
+        opt = lambda a, name: None if a is None else self._real(a, (a.shape[0],), name)
+        self._chk(self.lib.ecwam_hip_recvnemofields(self._h, int(kijs), int(kijl), int(flags), self._fieldg(fieldg), dbl(nemo, (4, kijl), "NEMO"),
+                                                    dbl(nemoibr, (kijl,), "NEMOIBR"), None if ff is None else self._real(ff, (ff.shape[0], NFF), "FF"),
+                                                    opt(ucur, "UCUR"), opt(vcur, "VCUR"),
+                                                    None if intf is None else self._real(intf, (intf.shape[0], NINTF), "INTF"), _stream_ptr()))
+
+    def updnemo(self, kijs, kijl, wam2nemo, nemontau: int, fields7=None, stress6=None):
+        """UPDNEMOFIELDS into fields7 (float64 [7][ld]: NSWH, NMWP, NPHIEPS, NTAUOC, NEMOSTRN, NEMOUSTOKES, NEMOVSTOKES) and UPDNEMOSTRESS into stress6
+        (float64 [6][ld]: NEMOTAUX, NEMOTAUY, NEMOWSWAVE, NEMOPHIF, NEMOTAUICX, NEMOTAUICY, each times 1 / nemontau; zeros with nemontau <= 0), from
+        rows [kijs, kijl) of wam2nemo (float64 [>= kijl][13]), whose six accumulated columns become 0 with stress6.  Either output may be None."""
+        if not (wam2nemo.is_cuda and wam2nemo.dtype == torch.float64 and wam2nemo.is_contiguous() and wam2nemo.dim() == 2 and wam2nemo.shape[1] == 13
+                and 0 <= kijs <= kijl <= wam2nemo.shape[0]):
+            raise ValueError("WAM2NEMO: expected a contiguous float64 cuda tensor [>= KIJL][13]")
+        ld = None
+        for a, nf, name in ((fields7, 7, "FIELDS7"), (stress6, 6, "STRESS6")):
+            if a is None:
+                continue
+            if not (a.is_cuda and a.dtype == torch.float64 and a.is_contiguous() and a.dim() == 2 and a.shape[0] == nf and a.shape[1] >= kijl
+                    and ld in (None, a.shape[1])):
+                raise ValueError(f"{name}: expected a contiguous float64 cuda tensor [{nf}][ld], ld >= KIJL and the same for both outputs")
+            ld = a.shape[1]
+        self._chk(self.lib.ecwam_hip_updnemo(self._h, int(kijs), int(kijl), wam2nemo.data_ptr(), int(nemontau), None if fields7 is None else fields7.data_ptr(),
+                                             None if stress6 is None else stress6.data_ptr(), int(ld if ld is not None else kijl), _stream_ptr()))
 
     # -- GRIB-ready spectra and parameter fields (include/ecwam_hip_gribout.h; csrc/gribout.hip): from FL1 and BOUT to the encoder's VALUES
     def set_grib_map(self, ival, ntencode: int, poles=None) -> None:

@@ -97,6 +97,11 @@ struct ecwam_hip_ctx {
   int* fmap_out = nullptr;
   int fmap_n = 0;
   size_t fmap_ncell_in = 0, fmap_ncell_out = 0;
+  // ecwam_hip_set_fldinter (csrc/intake.hip): the validated table on the device -- the source positions int [fli_n][4] and the weights, reals
+  // [fli_n][4] (nullptr without interpolation)
+  int* fli_idx = nullptr;
+  void* fli_w = nullptr;
+  int fli_n = 0, fli_ngptotg = 0, fli_interpol = 0;
   // ecwam_hip_set_grib_map (csrc/gribout.hip): the validated map on the device (gmap.ival == nullptr: none), its rows, the scratch of the maxima
   GribMapDev gmap = {};
   int gmap_n = 0;
@@ -544,6 +549,8 @@ int ecwam_hip_destroy(ecwam_hip_ctx* c) {
   if (c->adv_dir) (void)hipFree(c->adv_dir);
   if (c->fmap_in) (void)hipFree(c->fmap_in);
   if (c->fmap_out) (void)hipFree(c->fmap_out);
+  if (c->fli_idx) (void)hipFree(c->fli_idx);
+  if (c->fli_w) (void)hipFree(c->fli_w);
   grib_map_free(c);
   halo_release(c);
   delete c;
@@ -970,6 +977,13 @@ static int seam_checks(ecwam_hip_ctx* c, const std::string& who, int kijs, int k
     if (b.used && ((uintptr_t)b.p % 16) != 0) return fail(who + ": the buffers must be 16-byte aligned");
   return 0;
 }
+static void fldinter_free(ecwam_hip_ctx* c) {
+  if (c->fli_idx) (void)hipFree(c->fli_idx);
+  if (c->fli_w) (void)hipFree(c->fli_w);
+  c->fli_idx = nullptr;
+  c->fli_w = nullptr;
+  c->fli_n = c->fli_ngptotg = c->fli_interpol = 0;
+}
 int ecwam_hip_set_forcing_map(ecwam_hip_ctx* c, int npts, const int* ixy_in, int ncell_in, const int* ixy_out, int ncell_out) {
   if (!c) return fail("null context");
   if (npts < 0) return fail("ecwam_hip_set_forcing_map: negative count");
@@ -990,6 +1004,7 @@ int ecwam_hip_set_forcing_map(ecwam_hip_ctx* c, int npts, const int* ixy_in, int
   if (c->fmap_in) { (void)hipFree(c->fmap_in); c->fmap_in = nullptr; }
   if (c->fmap_out) { (void)hipFree(c->fmap_out); c->fmap_out = nullptr; }
   c->fmap_n = npts; c->fmap_ncell_in = c->fmap_ncell_out = 0;
+  fldinter_free(c);      // the table of ecwam_hip_set_fldinter was checked against the map that goes
   const size_t bytes = (size_t)(npts > 0 ? npts : 1) * sizeof(int);
   if (ixy_in) {
     HIPCHK(hipMalloc((void**)&c->fmap_in, bytes));
@@ -1069,6 +1084,129 @@ int ecwam_hip_fldtoifs(ecwam_hip_ctx* c, int kijs, int kijl, const void* wvblock
   in_precision(c, [&](auto t) {
     launch_fldtoifs<decltype(t)>(kijs, kijl, c->fmap_out, wvblock, ld, nwvfields, defval, grid, c->fmap_ncell_out, (hipStream_t)stream);
   });
+  return launched();
+}
+
+// The forcing intake (include/ecwam_hip_intake.h; csrc/intake.hip)
+int ecwam_hip_set_fldinter(ecwam_hip_ctx* c, int npts, int ngptotg, const int* idx, const double* w, int interpol) {
+  if (!c) return fail("null context");
+  const std::string who = "ecwam_hip_set_fldinter";
+  if (idx) {
+    if (npts < 0) return fail(who + ": negative count");
+    if (ngptotg < 1) return fail(who + ": the fields need at least one point");
+    if (interpol && !w) return fail(who + ": the interpolation needs its weights");
+    if (!c->fmap_in) return fail(who + ": no inbound map");
+    if (npts != c->fmap_n) return fail(who + ": the inbound map has " + std::to_string(c->fmap_n) + " rows, the table " + std::to_string(npts));
+    // the rows must write distinct cells: the validated map is read back (a setter may wait)
+    HIPCHK(hipSetDevice(c->device));
+    std::vector<int> map((size_t)(npts > 0 ? npts : 1), 0);
+    if (npts > 0) HIPCHK(hipMemcpy(map.data(), c->fmap_in, (size_t)npts * sizeof(int), hipMemcpyDeviceToHost));
+    std::vector<unsigned char> seen(c->fmap_ncell_in, 0);
+    for (int i = 0; i < npts; i++) {
+      const int cell = map[(size_t)i];
+      if (seen[(size_t)cell]) return fail(who + ": row " + std::to_string(i) + " of the inbound map names a cell twice (two rows would write one cell)");
+      seen[(size_t)cell] = 1;
+    }
+    for (int i = 0; i < npts; i++)
+      for (int k = 0; k < (interpol ? 4 : 1); k++)
+        if (idx[4 * (size_t)i + k] < 0 || idx[4 * (size_t)i + k] >= ngptotg)
+          return fail(who + ": index " + std::to_string(k) + " of row " + std::to_string(i) + " outside [0, ngptotg)");
+    if (interpol && c->real_bytes == 4)      // the library narrows the weights back: nothing may be lost
+      for (size_t i = 0; i < 3 * (size_t)npts; i++)
+        if ((double)(float)w[i] != w[i])
+          return fail(who + ": weight " + std::to_string(i % 3) + " of row " + std::to_string(i / 3) + " is not a value of the working precision");
+  }
+  HIPCHK(hipSetDevice(c->device));
+  HIPCHK(hipDeviceSynchronize());      // a copy another stream may still read is not freed under it
+  fldinter_free(c);
+  if (!idx) return 0;
+  const size_t n = (size_t)(npts > 0 ? npts : 1);
+  std::vector<int> hi(4 * n, 0);
+  for (int i = 0; i < npts; i++)
+    for (int k = 0; k < 4; k++) hi[4 * (size_t)i + k] = idx[4 * (size_t)i + (interpol ? k : 0)];
+  // a failure half way leaves no table, not half of one
+  auto upload = [&]() -> int {
+    HIPCHK(hipMalloc((void**)&c->fli_idx, 4 * n * sizeof(int)));
+    HIPCHK(hipMemcpy(c->fli_idx, hi.data(), 4 * n * sizeof(int), hipMemcpyHostToDevice));
+    if (!interpol) return 0;
+    HIPCHK(hipMalloc(&c->fli_w, 4 * n * (size_t)c->real_bytes));
+    return in_precision(c, [&](auto t) {
+      std::vector<decltype(t)> hw(4 * n, 0);
+      for (int i = 0; i < npts; i++)
+        for (int k = 0; k < 3; k++) hw[4 * (size_t)i + k] = (decltype(t))w[3 * (size_t)i + k];
+      HIPCHK(hipMemcpy(c->fli_w, hw.data(), 4 * n * sizeof(decltype(t)), hipMemcpyHostToDevice));
+      return 0;
+    });
+  };
+  if (int rc = upload()) {
+    fldinter_free(c);
+    return rc;
+  }
+  c->fli_n = npts; c->fli_ngptotg = ngptotg; c->fli_interpol = interpol != 0;
+  return 0;
+}
+int ecwam_hip_fldinter(ecwam_hip_ctx* c, int kijs, int kijl, const void* fields, int ngptotg, int nfields, int flags, double roair, double wstar0, double pmiss,
+                       void* fieldg, int* mask_in, void* stream) {
+  if (!c) return fail("null context");
+  const std::string who = "ecwam_hip_fldinter";
+  const int all = ECWAM_HIP_FLI_LADEN | ECWAM_HIP_FLI_LGUST | ECWAM_HIP_FLI_LLKC | ECWAM_HIP_FLI_LWCUR | ECWAM_HIP_FLI_NEWCURR;
+  if (kijl < kijs || kijs < 0 || (c->fli_idx && kijl > c->fli_n)) return fail(who + ": bad range");      // rows beyond the table
+  if (flags & ~all) return fail(who + ": unknown flags");
+  if (!c->fli_idx) return fail(who + ": no table");
+  if (ngptotg != c->fli_ngptotg) return fail(who + ": ngptotg is " + std::to_string(ngptotg) + ", the table's " + std::to_string(c->fli_ngptotg));
+  const bool cur = (flags & ECWAM_HIP_FLI_NEWCURR) && (flags & ECWAM_HIP_FLI_LWCUR);
+  if (nfields < (cur ? 10 : 8)) return fail(who + ": nfields is smaller than the switches need (" + std::to_string(cur ? 10 : 8) + ")");
+  if (int rc = seam_checks(c, who, kijs, kijl, "inbound", {{fields, true}, {fieldg, true}})) return rc;
+  if (((uintptr_t)mask_in % 16) != 0) return fail(who + ": the buffers must be 16-byte aligned");
+  in_precision(c, [&](auto t) {
+    launch_fldinter<decltype(t)>(kijs, kijl, c->fli_idx, c->fli_w, c->fli_interpol, c->fmap_in, fields, (size_t)ngptotg, flags, roair, wstar0, pmiss, fieldg,
+                                 c->fmap_ncell_in, mask_in, (hipStream_t)stream);
+  });
+  return launched();
+}
+int ecwam_hip_init_fieldg(ecwam_hip_ctx* c, void* fieldg, int ncell, double roair, double wstar0, void* stream) {
+  if (!c) return fail("null context");
+  const std::string who = "ecwam_hip_init_fieldg";
+  if (ncell < 0) return fail(who + ": bad range");
+  HIPCHK(hipSetDevice(c->device));
+  if (ncell > 0 && !fieldg) return fail(who + ": null pointer");
+  if (((uintptr_t)fieldg % 16) != 0) return fail(who + ": the buffers must be 16-byte aligned");
+  in_precision(c, [&](auto t) { launch_init_fieldg<decltype(t)>(c->dtab, fieldg, (size_t)ncell, roair, wstar0, (hipStream_t)stream); });
+  return launched();
+}
+int ecwam_hip_recvnemofields(ecwam_hip_ctx* c, int kijs, int kijl, int flags, const void* fieldg, double* nemo, double* nemoibr, void* ff, void* ucur, void* vcur,
+                             void* intf, void* stream) {
+  if (!c) return fail("null context");
+  const std::string who = "ecwam_hip_recvnemofields";
+  const int all = ECWAM_HIP_RNF_LREST | ECWAM_HIP_RNF_LINIT | ECWAM_HIP_RNF_LWCOU | ECWAM_HIP_RNF_LWNEMOCOUCIC | ECWAM_HIP_RNF_LWNEMOCOUCIT |
+                  ECWAM_HIP_RNF_LWNEMOCOUCUR | ECWAM_HIP_RNF_LWNEMOCOUIBR;
+  const bool lake = (flags & ECWAM_HIP_RNF_LINIT) && (flags & ECWAM_HIP_RNF_LWCOU);      // the branch that reads the map
+  if (kijl < kijs || kijs < 0 || (lake && c->fmap_in && kijl > c->fmap_n)) return fail(who + ": bad range");
+  if (flags & ~all) return fail(who + ": unknown flags");
+  const bool rest = flags & ECWAM_HIP_RNF_LREST, init = flags & ECWAM_HIP_RNF_LINIT, cou = flags & ECWAM_HIP_RNF_LWCOU;
+  const bool cic = flags & ECWAM_HIP_RNF_LWNEMOCOUCIC, cit = flags & ECWAM_HIP_RNF_LWNEMOCOUCIT, cur = flags & ECWAM_HIP_RNF_LWNEMOCOUCUR;
+  const bool ibr = flags & ECWAM_HIP_RNF_LWNEMOCOUIBR;
+  if (!rest && !init) return fail(who + ": neither LREST nor LINIT");
+  // the branches that read LKFR through the map, in the kernel as here (IBRMEM takes NEMO's value on either side and reads neither)
+  const bool grid = init && cou && (cic || cit || cur);
+  const bool b_nemo = rest || (init && (cic || cit || cur)), b_ibr = ibr, b_ff = rest || (init && (cic || cit)), b_cur = rest || (init && cur);
+  if (int rc = seam_checks(c, who, kijs, kijl, init && cou ? "inbound" : nullptr,
+                           {{fieldg, grid}, {nemo, b_nemo}, {nemoibr, b_ibr}, {ff, b_ff}, {ucur, b_cur}, {vcur, b_cur}, {intf, ibr}}))
+    return rc;
+  in_precision(c, [&](auto t) {
+    launch_recvnemofields<decltype(t)>(kijs, kijl, flags, c->fmap_in, fieldg, c->fmap_ncell_in, nemo, nemoibr, ff, ucur, vcur, intf, (hipStream_t)stream);
+  });
+  return launched();
+}
+int ecwam_hip_updnemo(ecwam_hip_ctx* c, int kijs, int kijl, double* wam2nemo, int nemontau, double* fields7, double* stress6, int ld, void* stream) {
+  if (!c) return fail("null context");
+  const std::string who = "ecwam_hip_updnemo";
+  if (kijl < kijs || kijs < 0 || ld < kijl) return fail(who + ": bad range");
+  if (int rc = seam_checks(c, who, kijs, kijl, nullptr, {{wam2nemo, fields7 || stress6}})) return rc;
+  if (((uintptr_t)fields7 % 16) != 0 || ((uintptr_t)stress6 % 16) != 0) return fail(who + ": the buffers must be 16-byte aligned");
+  // ZNEMONTAUM1 = 1.0_JWRB / NEMONTAU
+  const double m1 = nemontau > 0 ? in_precision(c, [&](auto t) { return (double)((decltype(t))1 / (decltype(t))nemontau); }) : 0.0;
+  launch_updnemo(kijs, kijl, wam2nemo, nemontau > 0, m1, fields7, stress6, ld, (hipStream_t)stream);
   return launched();
 }
 

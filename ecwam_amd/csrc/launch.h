@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/ecwam_hip_forcing.h"
+#include "../../include/ecwam_hip_intake.h"
 #include "../../include/ecwam_hip_gribin.h"
 #include "../../include/ecwam_hip_gribout.h"
 #include "implsch_adv_args.h"
@@ -133,6 +134,16 @@ template <typename T> void launch_wvblock(const void* tab, int llgcbz0, int kijs
         void* wvblock, int ld, hipStream_t s);
 template <typename T> void launch_fldtoifs(int kijs, int kijl, const int* map, const void* wvblock, int ld, int nwvfields, const double* defval, void* grid, size_t ncell,
         hipStream_t s);
+
+// ---- intake.hip: the forcing intake (include/ecwam_hip_intake.h).  idx = int [npts][4] and wgt = reals [npts][4] (DJ1, DII1, DIIP1, padding): the validated
+// table of ecwam_hip_set_fldinter on the device; map, ncell, nemo as above.  An empty range launches nothing. -------------------------------------------------
+template <typename T> void launch_fldinter(int kijs, int kijl, const void* idx, const void* wgt, int interpol, const int* map, const void* fields, size_t ngptotg,
+        int flags, double roair, double wstar0, double pmiss, void* fieldg, size_t ncell, int* mask_in, hipStream_t s);
+template <typename T> void launch_init_fieldg(const void* tab, void* fieldg, size_t ncell, double roair, double wstar0, hipStream_t s);
+template <typename T> void launch_recvnemofields(int kijs, int kijl, int flags, const int* map, const void* fieldg, size_t ncell, double* nemo, double* nemoibr,
+        void* ff, void* ucur, void* vcur, void* intf, hipStream_t s);
+// scale = 0: the stresses are zeros (NEMONTAU <= 0); znemontaum1 = 1 / NEMONTAU, formed in the working precision
+void launch_updnemo(int kijs, int kijl, double* wam2nemo, int scale, double znemontaum1, double* fields7, double* stress6, int ld, hipStream_t s);
 
 // ---- gribout.hip: GRIB-ready spectra and parameter fields (include/ecwam_hip_gribout.h).  GribMapDev = the validated map of ecwam_hip_set_grib_map on the
 // device: ival [npts] row -> cell, unfilled [nunf] the cells no row fills (those of a padded pole row excepted), adj [north.nadj + south.nadj] cell -> row

@@ -106,6 +106,12 @@ class GribOpts(C.Structure):
 EXPORTS_GRIBIN = ["ecwam_hip_getspec_values", "ecwam_hip_getspec_unpack"]
 GETSPEC_UNSCALE, GETSPEC_MISSING = 1, 2
 
+# include/ecwam_hip_intake.h: the forcing intake in front of GETWND and the hand-over to NEMO (INIT_FIELDG, FLDINTER, RECVNEMOFIELDS, UPDNEMO*), added to
+# ABI 6 in the same way
+EXPORTS_INTAKE = ["ecwam_hip_set_fldinter", "ecwam_hip_fldinter", "ecwam_hip_init_fieldg", "ecwam_hip_recvnemofields", "ecwam_hip_updnemo"]
+FLI_LADEN, FLI_LGUST, FLI_LLKC, FLI_LWCUR, FLI_NEWCURR = 1, 2, 4, 8, 16
+RNF_LREST, RNF_LINIT, RNF_LWCOU, RNF_LWNEMOCOUCIC, RNF_LWNEMOCOUCIT, RNF_LWNEMOCOUCUR, RNF_LWNEMOCOUIBR = 1, 2, 4, 8, 16, 32, 64
+
 ABI_VERSION = 6        # include/ecwam_hip.h ECWAM_HIP_ABI_VERSION
 _lib = None
 
@@ -217,6 +223,13 @@ def load() -> C.CDLL:
     for name in EXPORTS_GRIBIN:
         getattr(lib, name).restype = C.c_int
         getattr(lib, name).argtypes = [vp, ci, ci, vp, ll, ci, ci, ci, C.POINTER(GribOpts), vp, vp]
+    for name in EXPORTS_INTAKE:
+        getattr(lib, name).restype = C.c_int
+    lib.ecwam_hip_set_fldinter.argtypes = [vp, ci, ci, vp, vp, ci]
+    lib.ecwam_hip_fldinter.argtypes = [vp, ci, ci, vp, ci, ci, ci, cd, cd, cd, vp, vp, vp]
+    lib.ecwam_hip_init_fieldg.argtypes = [vp, vp, ci, cd, cd, vp]
+    lib.ecwam_hip_recvnemofields.argtypes = [vp, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.ecwam_hip_updnemo.argtypes = [vp, ci, ci, vp, ci, vp, vp, ci, vp]
     _lib = lib
     return lib
 

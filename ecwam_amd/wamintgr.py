@@ -729,6 +729,45 @@ class Wamintgr:
         self.ctx.fldtoifs(0, self.n, wvblock, grid, defval)
         return grid
 
+    # ---- the forcing intake (csrc/intake.hip): INIT_FIELDG, IFSTOWAM's FLDINTER and RECVNEMOFIELDS in front of getwnd(), UPDNEMOFIELDS and
+    # UPDNEMOSTRESS behind the step.  The exchange with the IFS and with NEMO, IJBLOCK and INITIALINT's once-per-run tables stay with the host.
+    def set_fldinter(self, idx, w=None, ngptotg: int = 0, interpol: bool = True) -> None:
+        """The per-point table of FLDINTER for the local rows (intake.point_table), after set_forcing_map()."""
+        if idx is not None and np.asarray(idx).shape[0] != self.n:
+            raise ValueError("set_fldinter: one table row per local row")
+        self.ctx.set_fldinter(idx, w, ngptotg, interpol)
+
+    def init_fieldg(self, ncell: int | None = None, roair: float = 1.225, wstar0: float = 0.0) -> torch.Tensor:
+        """INIT_FIELDG with LLINIALL on a new (or the resident) fieldg [13][ncell]; ncell defaults to the inbound map's."""
+        ncell = int(getattr(self.ctx, "_fmap", (0, 0, 0))[1] if ncell is None else ncell)
+        if getattr(self, "fieldg", None) is None or tuple(self.fieldg.shape) != (api.NFIELDG, ncell):
+            self.fieldg = torch.empty((api.NFIELDG, ncell), dtype=self.dtype, device=self.dev)
+        self.ctx.init_fieldg(self.fieldg, roair, wstar0)
+        return self.fieldg
+
+    def ifstowam(self, fields, mask_in=None, **switches) -> torch.Tensor:
+        """IFSTOWAM's arithmetic: FLDINTER of fields [nfields][ngptotg] (a cuda tensor of the working precision) into the resident fieldg, which
+        init_fieldg() creates on the first call.  switches: those of HipContext.fldinter (laden, lgust, llkc, lwcur, newcurr, roair, wstar0,
+        pmiss).  Returns fieldg, what getwnd(), adswstar() and getcurr() take."""
+        if getattr(self, "fieldg", None) is None:
+            self.init_fieldg(roair=switches.get("roair", 1.225), wstar0=switches.get("wstar0", 0.0))
+        self.ctx.fldinter(0, self.n, fields, self.fieldg, mask_in=mask_in, **switches)
+        return self.fieldg
+
+    def recvnemofields(self, nemo, nemoibr=None, fieldg=None, **switches) -> None:
+        """RECVNEMOFIELDS on the resident FF_NOW, currents and INTFLDS (IBRMEM); nemo float64 [4][n], nemoibr float64 [n].  fieldg defaults to the
+        resident one.  switches: lrest, linit, lwcou, lwnemocoucic, lwnemocoucit, lwnemocoucur, lwnemocouibr."""
+        u, v = self._currents()
+        self.ctx.recvnemofields(0, self.n, nemo, self.ff, u, v, self.intf, getattr(self, "fieldg", None) if fieldg is None else fieldg, nemoibr, **switches)
+
+    def updnemo(self, wam2nemo, nemontau: int, fields: bool = True, stress: bool = True):
+        """UPDNEMOFIELDS and UPDNEMOSTRESS on the WAVE2OCEAN block of the step: (fields7 [7][n] or None, stress6 [6][n] or None), float64; with
+        stress the six accumulated columns of wam2nemo become 0 (NEMONTAU = 0 is the caller's)."""
+        f7 = torch.empty((7, self.n), dtype=torch.float64, device=self.dev) if fields else None
+        s6 = torch.empty((6, self.n), dtype=torch.float64, device=self.dev) if stress else None
+        self.ctx.updnemo(0, self.n, wam2nemo, nemontau, f7, s6)
+        return f7, s6
+
     # ---- GRIB-ready output (csrc/gribout.hip): OUTSPEC and OUTINT up to the vector VALUES the encoder takes.  eccodes, the dates, the exchange
     # between tasks and FDB stay with the host.
     def set_grib_map(self, ival=None, ntencode: int | None = None, poles=None, lpadpoles: bool = True) -> None:

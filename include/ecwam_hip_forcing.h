@@ -63,7 +63,8 @@ typedef struct ecwam_hip_forcing_opts {
  * Either may be NULL: that map is then removed, and a call that needs it refuses ("no inbound map", "no outbound map").  The library validates on
  * the host and uploads: no kernel ever reads an unchecked index.
  * Refused: npts < 0, ncell < 1 beside a map, an index outside [0, ncell), a duplicate in ixy_out (two writers to one cell would make the
- * scatter depend on their order). */
+ * scatter depend on their order).
+ * The per-point table of FLDINTER (the setter of ecwam_hip_intake.h) was checked against the inbound map it found: an accepted call here removes it. */
 int ecwam_hip_set_forcing_map(ecwam_hip_ctx *ctx, int npts, const int *ixy_in, int ncell_in, const int *ixy_out, int ncell_out);
 
 /* GETWND per chunk (getwnd.F90:211-229): WAMWND (wamwnd.F90:126-294) followed by MICEP (micep.F90:116-254), in one kernel.  Whether ff is the NOW
