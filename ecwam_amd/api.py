@@ -550,6 +550,61 @@ class HipContext:
         self._chk(self.lib.ecwam_hip_updnemo(self._h, int(kijs), int(kijl), wam2nemo.data_ptr(), int(nemontau), None if fields7 is None else fields7.data_ptr(),
                                              None if stress6 is None else stress6.data_ptr(), int(ld if ld is not None else kijl), _stream_ptr()))
 
+    # -- the forcing of a stand-alone run (include/ecwam_hip_readwind.h; csrc/readwind.hip): GRIB2WGRID, READWIND's fill, CURRENT2WAM
+    def set_input_grid(self, slot: int, pos, w=None, kind=None, nvalues: int = 0, interpol: bool = True) -> None:
+        """The per-cell table of GRIB2WGRID for one input grid (readwind.cell_table builds it) in slot 0 .. 3: pos host integers [ncell][4], the
+        0-based positions in VALUES of the four corners (-1: a padded row); w host numbers [ncell][3], DK1, DII1, DIIP1 in the working precision;
+        kind host integers [ncell] (0 outside the row, 1 PMISS, 2 interpolate); nvalues the length of VALUES.  interpol=False is LLINTERPOL = F:
+        only pos[:, 0] is read.  pos=None removes the slot's table.  The library validates and uploads it."""
+        if pos is None:
+            self._chk(self.lib.ecwam_hip_set_input_grid(self._h, int(slot), 0, 0, None, None, None, 0))
+            return
+        a = np.ascontiguousarray(pos, dtype=np.int32)
+        if a.ndim != 2 or a.shape[1] != 4:
+            raise ValueError("set_input_grid: pos is [ncell][4]")
+        k = None if kind is None else np.ascontiguousarray(kind, dtype=np.int32).reshape(-1)
+        if k is not None and k.size != a.shape[0]:
+            raise ValueError("set_input_grid: one kind per cell")
+        pw = None
+        if w is not None:
+            pw = np.ascontiguousarray(w, dtype=np.float64)
+            if pw.shape != (a.shape[0], 3):
+                raise ValueError("set_input_grid: w is [ncell][3]")
+        self._chk(self.lib.ecwam_hip_set_input_grid(self._h, int(slot), a.shape[0], int(nvalues), a.ctypes.data_as(C.c_void_p),
+                                                    None if pw is None else pw.ctypes.data_as(C.c_void_p), None if k is None else k.ctypes.data_as(C.c_void_p),
+                                                    int(bool(interpol))))
+
+    def grib2wgrid(self, slot: int, values, fields, out=None, fieldg=None, roair: float = 1.225, wstar0: float = 0.0, pmiss: float = -999.0):
+        """GRIB2WGRID (grib2wgrid.F90:783-1130) of the decoded vectors values [nfld][vstride] through the table of the slot, in one launch.  fields:
+        per vector (target, flags) -- target lib.G2W_FIELD (FIELD as the routine returns it, into row f of out [nfld][ld]), or the name or number of a
+        plane of fieldg [13][ncell] (lib.G2W_PLANES), filled by READWIND's rule (readwind.F90:341-494); flags the lib.G2W_DIRFLD / G2W_NONWAVE bits."""
+        if values.dim() != 2 or len(fields) != values.shape[0]:
+            raise ValueError("GRIB2WGRID: values is [nfld][vstride], one (target, flags) per vector")
+        nf, vs = values.shape
+        desc = (_lib.G2wField * max(nf, 1))()
+        for f, (target, flags) in enumerate(fields):
+            desc[f].target = _lib.FG_PLANES.index(target) if isinstance(target, str) else int(target)
+            desc[f].flags = int(flags)
+        po = None if out is None else self._real(out, (nf, out.shape[-1]), "OUT")
+        pg = None
+        if fieldg is not None:
+            if fieldg.dim() != 2 or fieldg.shape[0] != len(_lib.FG_PLANES):
+                raise ValueError("FIELDG: expected [13][ncell]")
+            pg = self._real(fieldg, tuple(fieldg.shape), "FIELDG")
+        self._chk(self.lib.ecwam_hip_grib2wgrid(self._h, int(slot), self._real(values, (nf, vs), "VALUES"), vs, nf, desc, float(roair), float(wstar0), float(pmiss),
+                                                po, 0 if out is None else int(out.shape[-1]), pg, 0 if fieldg is None else int(fieldg.shape[1]), _stream_ptr()))
+
+    def current2wam(self, kijs, kijl, field_u, field_v, ucur, vcur, wlowest: float, zmiss: float = -999.0, changed=None):
+        """CURRENT2WAM's statements (current2wam.F90:253-259, 270-276) on rows [kijs, kijl) through the inbound map: field_u / field_v are FIELD
+        planes [ncell_in] of grib2wgrid; a component given as None is left alone.  changed as in getcurr."""
+        ncell = getattr(self, "_fmap", (0, 0, 0))[1]
+        self._seam("CURRENT2WAM", kijs, kijl, *[c for f, c in ((field_u, ucur), (field_v, vcur)) if f is not None])
+        fld = lambda a, name: None if a is None else self._real(a, (ncell,), name)
+        cur = lambda f, a, name: None if f is None else self._real(a, (a.shape[0],), name)
+        self._chk(self.lib.ecwam_hip_current2wam(self._h, int(kijs), int(kijl), fld(field_u, "FIELD_U"), fld(field_v, "FIELD_V"), float(wlowest), float(zmiss),
+                                                 cur(field_u, ucur, "UCUR"), cur(field_v, vcur, "VCUR"),
+                                                 None if changed is None else self._int(changed, (1,), "CHANGED"), _stream_ptr()))
+
     # -- GRIB-ready spectra and parameter fields (include/ecwam_hip_gribout.h; csrc/gribout.hip): from FL1 and BOUT to the encoder's VALUES
     def set_grib_map(self, ival, ntencode: int, poles=None) -> None:
         """ival: host integers, the 0-based position in VALUES of every row; poles: a gribout.Poles (or None: no padding).  gribout.value_map

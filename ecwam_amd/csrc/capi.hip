@@ -102,6 +102,14 @@ struct ecwam_hip_ctx {
   int* fli_idx = nullptr;
   void* fli_w = nullptr;
   int fli_n = 0, fli_ngptotg = 0, fli_interpol = 0;
+  // ecwam_hip_set_input_grid (csrc/readwind.hip): per slot the validated table on the device -- the positions int [ncell][4] and reals [ncell][4]: DK1, DII1,
+  // DIIP1 and the kind
+  struct G2wSlot {
+    int* pos = nullptr;
+    void* w = nullptr;
+    int ncell = 0, nvalues = 0, interpol = 0;
+  };
+  G2wSlot g2w[ECWAM_HIP_G2W_NSLOT];
   // ecwam_hip_set_grib_map (csrc/gribout.hip): the validated map on the device (gmap.ival == nullptr: none), its rows, the scratch of the maxima
   GribMapDev gmap = {};
   int gmap_n = 0;
@@ -551,6 +559,10 @@ int ecwam_hip_destroy(ecwam_hip_ctx* c) {
   if (c->fmap_out) (void)hipFree(c->fmap_out);
   if (c->fli_idx) (void)hipFree(c->fli_idx);
   if (c->fli_w) (void)hipFree(c->fli_w);
+  for (auto& g : c->g2w) {
+    if (g.pos) (void)hipFree(g.pos);
+    if (g.w) (void)hipFree(g.w);
+  }
   grib_map_free(c);
   halo_release(c);
   delete c;
@@ -1207,6 +1219,118 @@ int ecwam_hip_updnemo(ecwam_hip_ctx* c, int kijs, int kijl, double* wam2nemo, in
   // ZNEMONTAUM1 = 1.0_JWRB / NEMONTAU
   const double m1 = nemontau > 0 ? in_precision(c, [&](auto t) { return (double)((decltype(t))1 / (decltype(t))nemontau); }) : 0.0;
   launch_updnemo(kijs, kijl, wam2nemo, nemontau > 0, m1, fields7, stress6, ld, (hipStream_t)stream);
+  return launched();
+}
+
+// The forcing of a stand-alone run (include/ecwam_hip_readwind.h; csrc/readwind.hip)
+static void g2w_free(ecwam_hip_ctx::G2wSlot& g) {
+  if (g.pos) (void)hipFree(g.pos);
+  if (g.w) (void)hipFree(g.w);
+  g = ecwam_hip_ctx::G2wSlot{};
+}
+int ecwam_hip_set_input_grid(ecwam_hip_ctx* c, int slot, int ncell, int nvalues, const int* pos, const double* w, const int* kind, int interpol) {
+  if (!c) return fail("null context");
+  const std::string who = "ecwam_hip_set_input_grid";
+  if (slot < 0 || slot >= ECWAM_HIP_G2W_NSLOT) return fail(who + ": bad range");
+  if (pos) {
+    if (ncell < 0) return fail(who + ": negative count");
+    if (nvalues < 1) return fail(who + ": the message needs at least one value");
+    if (!kind) return fail(who + ": null pointer");
+    if (interpol && !w) return fail(who + ": the interpolation needs its weights");
+    for (int i = 0; i < ncell; i++) {
+      if (kind[i] < 0 || kind[i] > 2) return fail(who + ": kind of cell " + std::to_string(i) + " outside 0 .. 2");
+      for (int k = 0; k < (interpol ? 4 : 1); k++) {
+        const int p = pos[4 * (size_t)i + k];
+        if (p < -1 || p >= nvalues || (!interpol && kind[i] == 2 && p < 0))
+          return fail(who + ": position " + std::to_string(k) + " of cell " + std::to_string(i) + " outside [" + (interpol ? "-1" : "0") + ", nvalues)");
+      }
+    }
+    if (interpol)
+      for (size_t i = 0; i < 3 * (size_t)ncell; i++) {
+        if (!std::isfinite(w[i])) return fail(who + ": weight " + std::to_string(i % 3) + " of cell " + std::to_string(i / 3) + " is not finite");
+        if (c->real_bytes == 4 && (double)(float)w[i] != w[i])      // the library narrows the weights back: nothing may be lost
+          return fail(who + ": weight " + std::to_string(i % 3) + " of cell " + std::to_string(i / 3) + " is not a value of the working precision");
+      }
+  }
+  HIPCHK(hipSetDevice(c->device));
+  HIPCHK(hipDeviceSynchronize());      // a copy another stream may still read is not freed under it
+  ecwam_hip_ctx::G2wSlot& g = c->g2w[slot];
+  g2w_free(g);
+  if (!pos) return 0;
+  const size_t n = (size_t)(ncell > 0 ? ncell : 1);
+  std::vector<int> hp(4 * n, -1);
+  for (int i = 0; i < ncell; i++)
+    for (int k = 0; k < 4; k++) hp[4 * (size_t)i + k] = pos[4 * (size_t)i + (interpol ? k : 0)];
+  // a failure half way leaves no table, not half of one
+  auto upload = [&]() -> int {
+    HIPCHK(hipMalloc((void**)&g.pos, 4 * n * sizeof(int)));
+    HIPCHK(hipMemcpy(g.pos, hp.data(), 4 * n * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(hipMalloc(&g.w, 4 * n * (size_t)c->real_bytes));
+    return in_precision(c, [&](auto t) {
+      std::vector<decltype(t)> hw(4 * n, 0);
+      for (int i = 0; i < ncell; i++) {
+        for (int k = 0; interpol && k < 3; k++) hw[4 * (size_t)i + k] = (decltype(t))w[3 * (size_t)i + k];
+        hw[4 * (size_t)i + 3] = (decltype(t))kind[i];
+      }
+      HIPCHK(hipMemcpy(g.w, hw.data(), 4 * n * sizeof(decltype(t)), hipMemcpyHostToDevice));
+      return 0;
+    });
+  };
+  if (int rc = upload()) {
+    g2w_free(g);
+    return rc;
+  }
+  g.ncell = ncell; g.nvalues = nvalues; g.interpol = interpol != 0;
+  return 0;
+}
+int ecwam_hip_grib2wgrid(ecwam_hip_ctx* c, int slot, const void* values, int vstride, int nfld, const ecwam_hip_g2w_field* desc, double roair, double wstar0,
+                         double pmiss, void* out, int ld, void* fieldg, int ncell_in, void* stream) {
+  if (!c) return fail("null context");
+  const std::string who = "ecwam_hip_grib2wgrid";
+  if (slot < 0 || slot >= ECWAM_HIP_G2W_NSLOT) return fail(who + ": bad range");
+  const ecwam_hip_ctx::G2wSlot& g = c->g2w[slot];
+  if (!g.pos) return fail(who + ": no table");
+  if (vstride < g.nvalues) return fail(who + ": vstride is " + std::to_string(vstride) + ", the table's nvalues " + std::to_string(g.nvalues));
+  if (nfld < 1 || nfld > ECWAM_HIP_G2W_MAXFLD) return fail(who + ": nfld outside 1 .. 16");
+  if (!desc) return fail(who + ": null descriptors");
+  bool any_field = false, any_plane = false;
+  unsigned seen = 0;
+  for (int f = 0; f < nfld; f++) {
+    const int t = desc[f].target;
+    if (desc[f].flags & ~(ECWAM_HIP_G2W_DIRFLD | ECWAM_HIP_G2W_NONWAVE)) return fail(who + ": unknown flags of field " + std::to_string(f));
+    if (t == ECWAM_HIP_G2W_FIELD) {
+      any_field = true;
+      continue;
+    }
+    if (t != ECWAM_HIP_FG_UWND && t != ECWAM_HIP_FG_VWND && t != ECWAM_HIP_FG_AIRD && t != ECWAM_HIP_FG_WSTAR && t != ECWAM_HIP_FG_CICOVER &&
+        t != ECWAM_HIP_FG_CITHICK && t != ECWAM_HIP_FG_WSWAVE && t != ECWAM_HIP_FG_WDWAVE)
+      return fail(who + ": unknown target of field " + std::to_string(f));
+    if (seen & (1u << t)) return fail(who + ": field " + std::to_string(f) + " targets a plane a field before it fills (LLNOTREAD)");
+    seen |= 1u << t;
+    any_plane = true;
+  }
+  if (any_plane && ncell_in != g.ncell) return fail(who + ": ncell_in is " + std::to_string(ncell_in) + ", the table's ncell " + std::to_string(g.ncell));
+  if (any_field && ld < g.ncell) return fail(who + ": ld is smaller than the table's ncell");
+  HIPCHK(hipSetDevice(c->device));
+  if (g.ncell > 0 && (!values || (any_field && !out) || (any_plane && !fieldg))) return fail(who + ": null pointer");
+  if (((uintptr_t)values % 16) != 0 || (any_field && ((uintptr_t)out % 16) != 0) || (any_plane && ((uintptr_t)fieldg % 16) != 0))
+    return fail(who + ": the buffers must be 16-byte aligned");
+  in_precision(c, [&](auto t) {
+    launch_grib2wgrid<decltype(t)>(g.ncell, g.pos, g.w, g.interpol, values, (size_t)vstride, nfld, desc, roair, wstar0, pmiss, out, (size_t)(ld > 0 ? ld : 0), fieldg,
+                                   (size_t)g.ncell, (hipStream_t)stream);
+  });
+  return launched();
+}
+int ecwam_hip_current2wam(ecwam_hip_ctx* c, int kijs, int kijl, const void* field_u, const void* field_v, double wlowest, double zmiss, void* ucur, void* vcur,
+                          int* changed, void* stream) {
+  if (!c) return fail("null context");
+  const std::string who = "ecwam_hip_current2wam";
+  if (int rc = seam_checks(c, who, kijs, kijl, "inbound", {{field_u, false}, {field_v, false}, {ucur, field_u != nullptr}, {vcur, field_v != nullptr}})) return rc;
+  if (((uintptr_t)field_u % 16) != 0 || ((uintptr_t)field_v % 16) != 0) return fail(who + ": the buffers must be 16-byte aligned");
+  if (((uintptr_t)changed % sizeof(int)) != 0) return fail(who + ": the buffers must be 16-byte aligned");
+  in_precision(c, [&](auto t) {
+    launch_current2wam<decltype(t)>(kijs, kijl, c->fmap_in, field_u, field_v, wlowest, zmiss, ucur, vcur, changed, (hipStream_t)stream);
+  });
   return launched();
 }
 

@@ -10,6 +10,7 @@
 
 #include "../../include/ecwam_hip_forcing.h"
 #include "../../include/ecwam_hip_intake.h"
+#include "../../include/ecwam_hip_readwind.h"
 #include "../../include/ecwam_hip_gribin.h"
 #include "../../include/ecwam_hip_gribout.h"
 #include "implsch_adv_args.h"
@@ -144,6 +145,13 @@ template <typename T> void launch_recvnemofields(int kijs, int kijl, int flags, 
         void* ff, void* ucur, void* vcur, void* intf, hipStream_t s);
 // scale = 0: the stresses are zeros (NEMONTAU <= 0); znemontaum1 = 1 / NEMONTAU, formed in the working precision
 void launch_updnemo(int kijs, int kijl, double* wam2nemo, int scale, double znemontaum1, double* fields7, double* stress6, int ld, hipStream_t s);
+
+// ---- readwind.hip: the forcing of a stand-alone run (include/ecwam_hip_readwind.h).  pos = int [ncell][4] and wgt = reals [ncell][4] (DK1, DII1, DIIP1, the
+// kind): the validated table of ecwam_hip_set_input_grid on the device; desc is read on the host.  No cells, or no rows, launch nothing. ----------------------
+template <typename T> void launch_grib2wgrid(int ncell, const void* pos, const void* wgt, int interpol, const void* values, size_t vstride, int nfld,
+        const ecwam_hip_g2w_field* desc, double roair, double wstar0, double pmiss, void* out, size_t ld, void* fieldg, size_t ncell_in, hipStream_t s);
+template <typename T> void launch_current2wam(int kijs, int kijl, const int* map, const void* field_u, const void* field_v, double wlowest, double zmiss, void* ucur,
+        void* vcur, int* changed, hipStream_t s);
 
 // ---- gribout.hip: GRIB-ready spectra and parameter fields (include/ecwam_hip_gribout.h).  GribMapDev = the validated map of ecwam_hip_set_grib_map on the
 // device: ival [npts] row -> cell, unfilled [nunf] the cells no row fills (those of a padded pole row excepted), adj [north.nadj + south.nadj] cell -> row

@@ -112,6 +112,15 @@ EXPORTS_INTAKE = ["ecwam_hip_set_fldinter", "ecwam_hip_fldinter", "ecwam_hip_ini
 FLI_LADEN, FLI_LGUST, FLI_LLKC, FLI_LWCUR, FLI_NEWCURR = 1, 2, 4, 8, 16
 RNF_LREST, RNF_LINIT, RNF_LWCOU, RNF_LWNEMOCOUCIC, RNF_LWNEMOCOUCIT, RNF_LWNEMOCOUCUR, RNF_LWNEMOCOUIBR = 1, 2, 4, 8, 16, 32, 64
 
+# include/ecwam_hip_readwind.h: the forcing of a stand-alone run (GRIB2WGRID, READWIND's fill, CURRENT2WAM), added to ABI 6 in the same way
+EXPORTS_READWIND = ["ecwam_hip_set_input_grid", "ecwam_hip_grib2wgrid", "ecwam_hip_current2wam"]
+G2W_NSLOT, G2W_MAXFLD, G2W_FIELD, G2W_DIRFLD, G2W_NONWAVE = 4, 16, -1, 1, 2
+G2W_PLANES = ("UWND", "VWND", "AIRD", "WSTAR", "CICOVER", "CITHICK", "WSWAVE", "WDWAVE")      # the planes of fieldg a field may target
+
+
+class G2wField(C.Structure):      # ecwam_hip_g2w_field
+    _fields_ = [("target", C.c_int), ("flags", C.c_int)]
+
 ABI_VERSION = 6        # include/ecwam_hip.h ECWAM_HIP_ABI_VERSION
 _lib = None
 
@@ -230,6 +239,11 @@ def load() -> C.CDLL:
     lib.ecwam_hip_init_fieldg.argtypes = [vp, vp, ci, cd, cd, vp]
     lib.ecwam_hip_recvnemofields.argtypes = [vp, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.ecwam_hip_updnemo.argtypes = [vp, ci, ci, vp, ci, vp, vp, ci, vp]
+    for name in EXPORTS_READWIND:
+        getattr(lib, name).restype = C.c_int
+    lib.ecwam_hip_set_input_grid.argtypes = [vp, ci, ci, ci, vp, vp, vp, ci]
+    lib.ecwam_hip_grib2wgrid.argtypes = [vp, ci, vp, ci, ci, C.POINTER(G2wField), cd, cd, cd, vp, ci, vp, ci, vp]
+    lib.ecwam_hip_current2wam.argtypes = [vp, ci, ci, vp, vp, cd, cd, vp, vp, vp, vp]
     _lib = lib
     return lib
 

@@ -768,6 +768,73 @@ class Wamintgr:
         self.ctx.updnemo(0, self.n, wam2nemo, nemontau, f7, s6)
         return f7, s6
 
+    # ---- the forcing of a stand-alone run (csrc/readwind.hip): READWIND and CURRENT2WAM behind the GRIB decoder.  The files, eccodes, the dates,
+    # LLNOTREAD across calls and READWIND's swamp branch stay with the host; ecwam_amd/readwind.py builds the table of an input grid.
+    READWIND_PLANES = {165: "UWND", 33: "UWND", 131: "UWND", 180: "UWND", 166: "VWND", 34: "VWND", 132: "VWND", 181: "VWND", 31: "CICOVER", 139: "CICOVER",
+                       92: "CITHICK", 245: "WSWAVE", 249: "WDWAVE", 209: "AIRD", 208: "WSTAR"}
+
+    def set_input_grid(self, slot: int, table) -> None:
+        """The table of one input grid (readwind.cell_table's dict: pos, w, kind, nvalues, interpol; None removes it) in slot 0 .. 3."""
+        if table is None:
+            self.ctx.set_input_grid(slot, None)
+            return
+        self.ctx.set_input_grid(slot, table["pos"], table["w"], table["kind"], table["nvalues"], table["interpol"])
+
+    def readwind(self, messages, slot: int = 0, roair: float = 1.225, wstar0: float = 0.0, llwswave: bool = False, llwdwave: bool = False, pmiss: float = -999.0):
+        """READWIND's loop over the decoded messages of one wind time (readwind.F90:272-494) into the resident fieldg, which init_fieldg() creates on
+        the first call: messages = [(paramId, values)] or [(paramId, values, flags)], values the vector as the decoder returned it (host numbers or
+        a cuda tensor), all of the input grid in `slot`.  IPARAM = paramId modulo 1000 chooses the plane (READWIND_PLANES); 245 and 249 are skipped
+        unless llwswave / llwdwave.  flags (lib.G2W_*) default to LLNONWAVE for a parameter of table 0 and to readwind.dirfld for one of table 140
+        (a wave stream).  Raises on a parameter it does not know, on 251, and on a plane filled twice.  Returns (fieldg, icode, iparamci): icode = 2
+        for 180 / 181 (stresses), else 3."""
+        from . import readwind as rw
+        if getattr(self, "fieldg", None) is None:
+            self.init_fieldg(roair=roair, wstar0=wstar0)
+        vecs, fields, seen, icode, iparamci = [], [], set(), 3, 0
+        for msg in messages:
+            param, values = int(msg[0]), msg[1]
+            iparam = param - (param // 1000) * 1000
+            if iparam == 251:
+                raise ValueError("readwind: parameter 251 (spectra) is un-scaled and read by getspec_values, not here")
+            plane = self.READWIND_PLANES.get(iparam)
+            if plane is None:
+                raise ValueError(f"readwind: suspicious wind or sea ice field param {iparam}")
+            if (iparam == 245 and not llwswave) or (iparam == 249 and not llwdwave):
+                continue
+            if plane in seen:
+                raise ValueError(f"readwind: parameter {iparam} fills {plane}, which a message before it has filled (LLNOTREAD)")
+            seen.add(plane)
+            if iparam in (180, 181):
+                icode = 2
+            elif plane in ("UWND", "VWND"):
+                icode = 3
+            if iparam in (31, 139):
+                iparamci = iparam
+            wave = param // 1000 == 140
+            flags = int(msg[2]) if len(msg) > 2 else ((api._lib.G2W_DIRFLD if rw.dirfld(iparam, True) else 0) if wave else api._lib.G2W_NONWAVE)
+            vecs.append(torch.as_tensor(np.asarray(values) if not torch.is_tensor(values) else values, dtype=self.dtype, device=self.dev).reshape(-1))
+            fields.append((plane, flags))
+        if vecs:
+            self.ctx.grib2wgrid(slot, torch.stack(vecs), fields, fieldg=self.fieldg, roair=roair, wstar0=wstar0, pmiss=pmiss)
+        return self.fieldg, icode, iparamci
+
+    def current2wam(self, u_values=None, v_values=None, slot: int = 0, wlowest: float = 0.0, zmiss: float = -999.0, flags: int | None = None) -> bool:
+        """CURRENT2WAM behind the decoder: the decoded U and V vectors of the input grid in `slot` (either may be None) through GRIB2WGRID and the
+        three statements of current2wam.F90:253-259 into the currents of the local rows.  True if any of them changed."""
+        given = [(k, v) for k, v in (("u", u_values), ("v", v_values)) if v is not None]
+        if not given:
+            return False
+        vec = torch.stack([torch.as_tensor(np.asarray(v) if not torch.is_tensor(v) else v, dtype=self.dtype, device=self.dev).reshape(-1) for _, v in given])
+        ncell = int(getattr(self.ctx, "_fmap", (0, 0, 0))[1])
+        out = torch.empty((len(given), -(-ncell // 4) * 4), dtype=self.dtype, device=self.dev)      # every FIELD begins a 16-byte piece
+        fl = api._lib.G2W_NONWAVE if flags is None else int(flags)
+        self.ctx.grib2wgrid(slot, vec, [(api._lib.G2W_FIELD, fl)] * len(given), out=out, pmiss=zmiss)
+        planes = {k: out[i, :ncell] for i, (k, _) in enumerate(given)}
+        u, v = self._currents()
+        changed = torch.zeros(1, dtype=torch.int32, device=self.dev)
+        self.ctx.current2wam(0, self.n, planes.get("u"), planes.get("v"), u, v, wlowest, zmiss, changed)
+        return bool(changed.item())
+
     # ---- GRIB-ready output (csrc/gribout.hip): OUTSPEC and OUTINT up to the vector VALUES the encoder takes.  eccodes, the dates, the exchange
     # between tasks and FDB stay with the host.
     def set_grib_map(self, ival=None, ntencode: int | None = None, poles=None, lpadpoles: bool = True) -> None:
