@@ -605,6 +605,73 @@ class HipContext:
                                                  cur(field_u, ucur, "UCUR"), cur(field_v, vcur, "VCUR"),
                                                  None if changed is None else self._int(changed, (1,), "CHANGED"), _stream_ptr()))
 
+    # -- the start and the end of a run (include/ecwam_hip_restart.h; csrc/restart.hip): INITDPTHFLDS, BUILDSTRESS, the restart fields and WRITEFL's record
+    def depthprpt(self, kijs, kijl, depth, wvprpt=None, wavnum=None, cgroup=None, omosnh2kd=None, ff=None, dkmax: float = 40.0, gam_b_j: float | None = None):
+        """INITDPTHFLDS with DEPTHPRPT and AKI on rows [kijs, kijl) from depth [>= kijl]: wvprpt [ij][5][NFRE] (WAVNUM, CGROUP, CINV, XK2CG, STOKFAC), the
+        extended arrays wavnum / cgroup / omosnh2kd [ij][NFRE], and EMAXDPT, DEPTH of ff.  Any output may be None, not all.  The land slot of depth holds
+        BATHYMAX and receives WVPRPT_LAND from the same call.  dkmax: yowpcons.F90; gam_b_j defaults to the tables'."""
+        outs = [a for a in (wvprpt, wavnum, cgroup, omosnh2kd, ff) if a is not None]
+        self._seam("DEPTHPRPT", kijs, kijl, depth, *outs)
+        o = _lib.DepthOpts(float(dkmax), float(self.t.GAM_B_J if gam_b_j is None else gam_b_j))
+        row = lambda a, name: None if a is None else self._real(a, (a.shape[0], self.NFRE), name)
+        self._chk(self.lib.ecwam_hip_depthprpt(self._h, int(kijs), int(kijl), self._real(depth, (depth.shape[0],), "DEPTH"), C.byref(o),
+                                               None if wvprpt is None else self._real(wvprpt, (wvprpt.shape[0], NWPR, self.NFRE), "WVPRPT"), row(wavnum, "WAVNUM"),
+                                               row(cgroup, "CGROUP"), row(omosnh2kd, "OMOSNH2KD"), None if ff is None else self._real(ff, (ff.shape[0], NFF), "FF"),
+                                               _stream_ptr()))
+
+    def buildstress(self, kijs, kijl, ff, uwave=None, cd=None, zref: float | None = None, z0b_zero: bool = True, nsestart: bool = False, prchar: float = 0.0185,
+                    zmiss: float = -999.0):
+        """BUILDSTRESS 1.2 to 1.5 with GETSTRESS's statements around it on rows [kijs, kijl) of ff: uwave / cd are planes [ncell_in] on the inbound map
+        (READWGRIB with LLONLYPOS) or None; zref is TEMPXNLEV (default XNLEV); z0b_zero: Z0B = 0; nsestart: CHRNCK = prchar, TAUW = 0."""
+        self._seam("BUILDSTRESS", kijs, kijl, ff)
+        ncell = getattr(self, "_fmap", (0, 0, 0))[1]
+        plane = lambda a, name: None if a is None else self._real(a, (ncell,), name)
+        flags = (_lib.BST_Z0B_ZERO if z0b_zero else 0) | (_lib.BST_NSESTART if nsestart else 0)
+        self._chk(self.lib.ecwam_hip_buildstress(self._h, int(kijs), int(kijl), plane(uwave, "UWAVE"), plane(cd, "CD"), float(self.t.XNLEV if zref is None else zref),
+                                                 flags, float(prchar), float(zmiss), self._real(ff, (ff.shape[0], NFF), "FF"), _stream_ptr()))
+
+    def set_restart_map(self, ij2newij) -> None:
+        """IJ2NEWIJ, 0-based host integers [npts]: position p of a vector in the global order holds row ij2newij[p].  None removes the map.  The library
+        validates that it is a permutation and uploads it."""
+        if ij2newij is None:
+            self._chk(self.lib.ecwam_hip_set_restart_map(self._h, 0, None))
+            self._rmap = 0
+            return
+        a = np.ascontiguousarray(ij2newij, dtype=np.int32).reshape(-1)
+        self._chk(self.lib.ecwam_hip_set_restart_map(self._h, a.size, a.ctypes.data_as(C.c_void_p)))
+        self._rmap = a.size
+
+    def _stress_fields(self, who, kijs, kijl, ff, ucur, vcur, rfield, relabel):
+        self._seam(who, kijs, kijl, ff, ucur, vcur)
+        if rfield.dim() != 2 or rfield.shape[0] != _lib.NRESTART_FIELDS or rfield.shape[1] < (getattr(self, "_rmap", 0) if relabel else kijl):
+            raise ValueError(f"{who}: expected RFIELD [16][ld] with ld >= the rows of the call (the points of the map with relabel)")
+        return (self._real(ff, (ff.shape[0], NFF), "FF"), self._real(ucur, (ucur.shape[0],), "UCUR"), self._real(vcur, (vcur.shape[0],), "VCUR"),
+                self._real(rfield, tuple(rfield.shape), "RFIELD"))
+
+    def savstress_pack(self, kijs, kijl, ff, ucur, vcur, rfield, relabel: bool = False):
+        """The sixteen restart fields of SAVSTRESS (savstress.F90:112-127) of rows [kijs, kijl) into rfield [16][ld]; relabel: through the restart map."""
+        pf, pu, pv, pr = self._stress_fields("SAVSTRESS", kijs, kijl, ff, ucur, vcur, rfield, relabel)
+        self._chk(self.lib.ecwam_hip_savstress_pack(self._h, int(kijs), int(kijl), pf, pu, pv, int(bool(relabel)), pr, int(rfield.shape[1]), _stream_ptr()))
+
+    def getstress_unpack(self, kijs, kijl, rfield, ff, ucur, vcur, relabel: bool = False):
+        """The inverse (getstress.F90:150-165): rfield [16][ld] into FF_NOW's columns of ff and the currents on rows [kijs, kijl)."""
+        pf, pu, pv, pr = self._stress_fields("GETSTRESS", kijs, kijl, ff, ucur, vcur, rfield, relabel)
+        self._chk(self.lib.ecwam_hip_getstress_unpack(self._h, int(kijs), int(kijl), pr, int(rfield.shape[1]), int(bool(relabel)), pf, pu, pv, _stream_ptr()))
+
+    def savspec_pack(self, kijs, kijl, fl1, blk, ifld0: int = 0, relabel: bool = False):
+        """WRITEFL's record: fields [ifld0, ifld0 + blk.shape[0]) (f = M NANG + K, up to NANG * NFRE) of rows [kijs, kijl) of FL1 into blk [nfld][ld], as
+        the values stand; relabel: row positions through the restart map (writefl.F90:117)."""
+        if blk.dim() != 2:
+            raise ValueError("SAVSPEC: expected BLK [nfld][ld]")
+        nfld, ld = blk.shape
+        nrow = fl1.shape[0]
+        if not (0 <= ifld0 and 1 <= nfld <= self.NANG * self.NFRE - ifld0):
+            raise ValueError(f"SAVSPEC: fields [{ifld0}, {ifld0 + nfld}) outside NANG * NFRE = {self.NANG * self.NFRE}")
+        if not (0 <= kijs <= kijl <= nrow) or ld < (getattr(self, "_rmap", 0) if relabel else kijl):
+            raise ValueError("SAVSPEC: KIJS/KIJL outside the operands, or vectors too short")
+        self._chk(self.lib.ecwam_hip_savspec_pack(self._h, int(kijs), int(kijl), self._real(fl1, (nrow, self.NANG, self.NFRE), "FL1"), int(ifld0), int(nfld),
+                                                  int(bool(relabel)), self._real(blk, (nfld, ld), "BLK"), int(ld), _stream_ptr()))
+
     # -- GRIB-ready spectra and parameter fields (include/ecwam_hip_gribout.h; csrc/gribout.hip): from FL1 and BOUT to the encoder's VALUES
     def set_grib_map(self, ival, ntencode: int, poles=None) -> None:
         """ival: host integers, the 0-based position in VALUES of every row; poles: a gribout.Poles (or None: no padding).  gribout.value_map

@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libecwam_hip.so")
-SOURCES = ["capi.hip", "propag.hip", "implsch4.hip", "implsch4a.hip", "implsch4x.hip", "implsch4r.hip", "implsch4rd.hip", "implsch4w.hip", "outbs.hip", "outbs_sep.hip", "outbs_ext.hip", "outbs_fl2nd.hip", "outbs_2nd.hip", "outbs_int.hip", "outblock.hip", "nest.hip", "start.hip", "forcing.hip", "intake.hip", "readwind.hip", "gribout.hip", "gribin.hip"]
+SOURCES = ["capi.hip", "propag.hip", "implsch4.hip", "implsch4a.hip", "implsch4x.hip", "implsch4r.hip", "implsch4rd.hip", "implsch4w.hip", "outbs.hip", "outbs_sep.hip", "outbs_ext.hip", "outbs_fl2nd.hip", "outbs_2nd.hip", "outbs_int.hip", "outblock.hip", "nest.hip", "start.hip", "forcing.hip", "intake.hip", "readwind.hip", "gribout.hip", "gribin.hip", "restart.hip"]
 # objects that are a second compilation of another source: object name -> (source, extra flags; a later -O overrides the earlier one).
 # implsch4r / implsch4rd = the single / double precision RARE builds of k_implsch4 (double precision: the two-kernel split, implsch4r.hip)
 DERIVED = {"implsch4r.hip": ("implsch4r.hip", ["-DV4R_PREC=1"]), "implsch4rd.hip": ("implsch4r.hip", ["-DV4R_PREC=2"])}
@@ -145,7 +145,7 @@ FSRC = os.path.join(HERE, "fortran")
 # the Fortran host layer: C interfaces + device state + transfer workers, the generated host types (tools/gen_yowdrvtype.py), the set-up
 # layer, the driver; then the harness programs (one executable each)
 FFILES = ["ecwam_hip_capi.F90", "yowdrvtype_hip.F90", "ecwam_hip_mod.F90", "ecwam_hip_restart.F90", "wamintgr_hip.F90", "harness_case.F90"]
-FPROGS = {"smoke_wamintgr_hip": "smoke_wamintgr_hip.F90", "seam_sequence": "seam_sequence.F90"}
+FPROGS = {"smoke_wamintgr_hip": "smoke_wamintgr_hip.F90", "seam_sequence": "seam_sequence.F90", "restart_check": "restart_check.F90"}
 
 
 def fortran_exe(prec: str, prog: str = "smoke_wamintgr_hip") -> str:

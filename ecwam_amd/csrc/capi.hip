@@ -110,6 +110,9 @@ struct ecwam_hip_ctx {
     int ncell = 0, nvalues = 0, interpol = 0;
   };
   G2wSlot g2w[ECWAM_HIP_G2W_NSLOT];
+  // ecwam_hip_set_restart_map (csrc/restart.hip): the inverse of the validated IJ2NEWIJ on the device -- row -> position in a vector of the global order
+  int* rmap_inv = nullptr;
+  int rmap_n = 0;
   // ecwam_hip_set_grib_map (csrc/gribout.hip): the validated map on the device (gmap.ival == nullptr: none), its rows, the scratch of the maxima
   GribMapDev gmap = {};
   int gmap_n = 0;
@@ -563,6 +566,7 @@ int ecwam_hip_destroy(ecwam_hip_ctx* c) {
     if (g.pos) (void)hipFree(g.pos);
     if (g.w) (void)hipFree(g.w);
   }
+  if (c->rmap_inv) (void)hipFree(c->rmap_inv);
   grib_map_free(c);
   halo_release(c);
   delete c;
@@ -1483,6 +1487,113 @@ int ecwam_hip_getspec_unpack(ecwam_hip_ctx* c, int kijs, int kijl, const void* b
                              void* stream) {
   if (!c) return fail("null context");
   return getspec_fields(c, "ecwam_hip_getspec_unpack", false, kijs, kijl, blk, ld, ifld0, nfld, flags, o, fl1, stream);
+}
+
+// The start and the end of a run (include/ecwam_hip_restart.h; csrc/restart.hip).  The checks of a call on rows after what the call itself refuses:
+// the range, then the buffers -- a16: 16-byte aligned; ar: aligned to a real; used: the call touches the buffer wherever the range is not empty (a
+// null pointer is refused then); the alignment is asked of every pointer that is given.  0 = go on.
+static int restart_checks(ecwam_hip_ctx* c, const std::string& who, int kijs, int kijl, int row_limit, std::initializer_list<SeamBuf> a16, std::initializer_list<SeamBuf> ar) {
+  if (kijl < kijs || kijs < 0 || (row_limit >= 0 && kijl > row_limit)) return fail(who + ": bad range");
+  HIPCHK(hipSetDevice(c->device));
+  for (const std::initializer_list<SeamBuf>& l : {a16, ar})
+    for (const SeamBuf& b : l)
+      if (kijl > kijs && b.used && !b.p) return fail(who + ": null pointer");
+  for (const SeamBuf& b : a16)
+    if (((uintptr_t)b.p % 16) != 0) return fail(who + ": the buffers must be 16-byte aligned");
+  for (const SeamBuf& b : ar)
+    if (((uintptr_t)b.p % c->real_bytes) != 0) return fail(who + ": the buffers must be aligned to a real");
+  return 0;
+}
+int ecwam_hip_depthprpt(ecwam_hip_ctx* c, int kijs, int kijl, const void* depth, const ecwam_hip_depth_opts* o, void* wvprpt, void* wavnum, void* cgroup, void* omosnh2kd,
+                        void* ff, void* stream) {
+  if (!c) return fail("null context");
+  const std::string who = "ecwam_hip_depthprpt";
+  if (!o) return fail(who + ": null options");
+  if (!wvprpt && !wavnum && !cgroup && !omosnh2kd && !ff) return fail(who + ": no output");
+  if (c->NFRE % (16 / c->real_bytes) != 0) return fail(who + ": the frequencies of a point are no whole number of 16-byte chunks");
+  if (int rc = restart_checks(c, who, kijs, kijl, -1, {{wvprpt, false}, {wavnum, false}, {cgroup, false}, {omosnh2kd, false}, {ff, false}}, {{depth, true}})) return rc;
+  in_precision(c, [&](auto t) {
+    return launch_depthprpt<decltype(t)>(c->dtab, kijs, kijl, depth, o->dkmax, o->gam_b_j, wvprpt, wavnum, cgroup, omosnh2kd, ff, c->NFRE, (hipStream_t)stream);
+  });
+  return launched();
+}
+int ecwam_hip_buildstress(ecwam_hip_ctx* c, int kijs, int kijl, const void* uwave, const void* cd, double zref, int flags, double prchar, double zmiss, void* ff,
+                          void* stream) {
+  if (!c) return fail("null context");
+  const std::string who = "ecwam_hip_buildstress";
+  if (flags & ~(ECWAM_HIP_BST_Z0B_ZERO | ECWAM_HIP_BST_NSESTART)) return fail(who + ": unknown flags");
+  const bool plane = uwave || cd;
+  if (plane && !c->fmap_in) return fail(who + ": no inbound map");
+  if (int rc = restart_checks(c, who, kijs, kijl, plane ? c->fmap_n : -1, {{ff, true}, {uwave, false}, {cd, false}}, {})) return rc;
+  in_precision(c, [&](auto t) {
+    launch_buildstress<decltype(t)>(c->dtab, kijs, kijl, c->fmap_in, uwave, cd, zref, flags, prchar, zmiss, ff, (hipStream_t)stream);
+  });
+  return launched();
+}
+int ecwam_hip_set_restart_map(ecwam_hip_ctx* c, int npts, const int* ij2newij) {
+  if (!c) return fail("null context");
+  const std::string who = "ecwam_hip_set_restart_map";
+  if (npts < 0) return fail(who + ": negative count");
+  std::vector<int> inv;
+  if (ij2newij) {
+    inv.assign((size_t)npts, -1);
+    for (int p = 0; p < npts; p++) {
+      const int r = ij2newij[p];
+      if (r < 0 || r >= npts) return fail(who + ": index " + std::to_string(p) + " outside [0, npts)");
+      if (inv[r] >= 0) return fail(who + ": index " + std::to_string(p) + " is a duplicate (no permutation)");
+      inv[r] = p;
+    }
+  }
+  HIPCHK(hipSetDevice(c->device));
+  // a copy another stream may still read is not freed under it
+  HIPCHK(hipDeviceSynchronize());
+  if (c->rmap_inv) { (void)hipFree(c->rmap_inv); c->rmap_inv = nullptr; }
+  c->rmap_n = 0;
+  if (ij2newij) {
+    HIPCHK(hipMalloc((void**)&c->rmap_inv, (size_t)(npts > 0 ? npts : 1) * sizeof(int)));
+    if (npts > 0) HIPCHK(hipMemcpy(c->rmap_inv, inv.data(), (size_t)npts * sizeof(int), hipMemcpyHostToDevice));
+    c->rmap_n = npts;
+  }
+  return 0;
+}
+// what the three calls on field vectors check of their positions: 0 = go on; row_limit and ld_min come back
+static int restart_positions(ecwam_hip_ctx* c, const std::string& who, int kijl, int relabel, int* row_limit, int* ld_min) {
+  if (relabel && !c->rmap_inv) return fail(who + ": no restart map");
+  *row_limit = relabel ? c->rmap_n : -1;
+  *ld_min = relabel ? c->rmap_n : kijl;
+  return 0;
+}
+static int stress_fields(ecwam_hip_ctx* c, const std::string& who, int pack, int kijs, int kijl, const void* ff, const void* ucur, const void* vcur, int relabel,
+                         const void* rfield, int ld, void* stream) {
+  int row_limit, ld_min;
+  if (int rc = restart_positions(c, who, kijl, relabel, &row_limit, &ld_min)) return rc;
+  if (ld < ld_min) return fail(who + ": bad range");
+  if (int rc = restart_checks(c, who, kijs, kijl, row_limit, {{ff, true}}, {{ucur, true}, {vcur, true}, {rfield, true}})) return rc;
+  in_precision(c, [&](auto t) {
+    launch_stress_fields<decltype(t)>(pack, kijs, kijl, relabel ? c->rmap_inv : nullptr, const_cast<void*>(ff), const_cast<void*>(ucur), const_cast<void*>(vcur),
+                                      const_cast<void*>(rfield), (size_t)ld, (hipStream_t)stream);
+  });
+  return launched();
+}
+int ecwam_hip_savstress_pack(ecwam_hip_ctx* c, int kijs, int kijl, const void* ff, const void* ucur, const void* vcur, int relabel, void* rfield, int ld, void* stream) {
+  if (!c) return fail("null context");
+  return stress_fields(c, "ecwam_hip_savstress_pack", 1, kijs, kijl, ff, ucur, vcur, relabel, rfield, ld, stream);
+}
+int ecwam_hip_getstress_unpack(ecwam_hip_ctx* c, int kijs, int kijl, const void* rfield, int ld, int relabel, void* ff, void* ucur, void* vcur, void* stream) {
+  if (!c) return fail("null context");
+  return stress_fields(c, "ecwam_hip_getstress_unpack", 0, kijs, kijl, ff, ucur, vcur, relabel, rfield, ld, stream);
+}
+int ecwam_hip_savspec_pack(ecwam_hip_ctx* c, int kijs, int kijl, const void* fl1, int ifld0, int nfld, int relabel, void* blk, int ld, void* stream) {
+  if (!c) return fail("null context");
+  const std::string who = "ecwam_hip_savspec_pack";
+  if (ifld0 < 0 || nfld < 1 || nfld > c->NANG * c->NFRE - ifld0) return fail(who + ": bad field range");
+  int row_limit, ld_min;
+  if (int rc = restart_positions(c, who, kijl, relabel, &row_limit, &ld_min)) return rc;
+  if (ld < ld_min) return fail(who + ": bad range");
+  if (int rc = restart_checks(c, who, kijs, kijl, row_limit, {{fl1, true}}, {{blk, true}})) return rc;
+  return grib_tile_done(who, in_precision(c, [&](auto t) {
+    return launch_savspec_pack<decltype(t)>(kijs, kijl, fl1, ifld0, nfld, relabel ? c->rmap_inv : nullptr, blk, (size_t)ld, c->NANG, c->NFRE, (hipStream_t)stream);
+  }));
 }
 
 // bit 0: the one-kernel step covers the context; bit 1: also with fast-wave sub-steps (gin); bit 2: also with the obstructions of

@@ -11,6 +11,7 @@
 #include "../../include/ecwam_hip_forcing.h"
 #include "../../include/ecwam_hip_intake.h"
 #include "../../include/ecwam_hip_readwind.h"
+#include "../../include/ecwam_hip_restart.h"
 #include "../../include/ecwam_hip_gribin.h"
 #include "../../include/ecwam_hip_gribout.h"
 #include "implsch_adv_args.h"
@@ -152,6 +153,17 @@ template <typename T> void launch_grib2wgrid(int ncell, const void* pos, const v
         const ecwam_hip_g2w_field* desc, double roair, double wstar0, double pmiss, void* out, size_t ld, void* fieldg, size_t ncell_in, hipStream_t s);
 template <typename T> void launch_current2wam(int kijs, int kijl, const int* map, const void* field_u, const void* field_v, double wlowest, double zmiss, void* ucur,
         void* vcur, int* changed, hipStream_t s);
+
+// ---- restart.hip: the start and the end of a run (include/ecwam_hip_restart.h).  map = the inbound map as above; inv = the inverse of the validated map of
+// ecwam_hip_set_restart_map on the device (row -> position in a vector of the global order), or nullptr: the row itself.  An empty range launches
+// nothing.  launch_depthprpt and launch_savspec_pack return as the tile launchers below. -----------------------------------------------------------------
+template <typename T> int launch_depthprpt(const void* tab, int kijs, int kijl, const void* depth, double dkmax, double gam_b_j, void* wvprpt, void* wavnum, void* cgroup,
+        void* omosnh2kd, void* ff, int NFRE, hipStream_t s);
+template <typename T> void launch_buildstress(const void* tab, int kijs, int kijl, const int* map, const void* uwave, const void* cd, double zref, int flags, double prchar,
+        double zmiss, void* ff, hipStream_t s);
+// pack != 0: ff, ucur, vcur -> rfield [16][ld]; otherwise the inverse
+template <typename T> void launch_stress_fields(int pack, int kijs, int kijl, const int* inv, void* ff, void* ucur, void* vcur, void* rfield, size_t ld, hipStream_t s);
+template <typename T> int launch_savspec_pack(int kijs, int kijl, const void* fl1, int ifld0, int nfld, const int* inv, void* blk, size_t ld, int NANG, int NFRE, hipStream_t s);
 
 // ---- gribout.hip: GRIB-ready spectra and parameter fields (include/ecwam_hip_gribout.h).  GribMapDev = the validated map of ecwam_hip_set_grib_map on the
 // device: ival [npts] row -> cell, unfilled [nunf] the cells no row fills (those of a padded pole row excepted), adj [north.nadj + south.nadj] cell -> row

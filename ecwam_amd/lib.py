@@ -121,6 +121,21 @@ G2W_PLANES = ("UWND", "VWND", "AIRD", "WSTAR", "CICOVER", "CITHICK", "WSWAVE", "
 class G2wField(C.Structure):      # ecwam_hip_g2w_field
     _fields_ = [("target", C.c_int), ("flags", C.c_int)]
 
+
+# include/ecwam_hip_restart.h: the start and the end of a run (INITDPTHFLDS, BUILDSTRESS, SAVSTRESS / GETSTRESS, WRITEFL's record), added to ABI 6 in the same way
+EXPORTS_RESTART = ["ecwam_hip_depthprpt", "ecwam_hip_buildstress", "ecwam_hip_set_restart_map", "ecwam_hip_savstress_pack", "ecwam_hip_getstress_unpack",
+                   "ecwam_hip_savspec_pack"]
+BST_Z0B_ZERO, BST_NSESTART = 1, 2
+NRESTART_FIELDS = 16
+# the columns of ff in the order of the restart fields (savstress.F90:112-125); UCUR and VCUR follow
+RESTART_FF_COLUMNS = (3, 1, 7, 8, 9, 10, 11, 12, 0, 4, 2, 13, 5, 6)
+
+
+class DepthOpts(C.Structure):
+    """ecwam_hip_depth_opts: DKMAX (yowpcons.F90) and GAM_B_J (yowshal.F90)"""
+    _fields_ = [("dkmax", C.c_double), ("gam_b_j", C.c_double)]
+
+
 ABI_VERSION = 6        # include/ecwam_hip.h ECWAM_HIP_ABI_VERSION
 _lib = None
 
@@ -244,6 +259,14 @@ def load() -> C.CDLL:
     lib.ecwam_hip_set_input_grid.argtypes = [vp, ci, ci, ci, vp, vp, vp, ci]
     lib.ecwam_hip_grib2wgrid.argtypes = [vp, ci, vp, ci, ci, C.POINTER(G2wField), cd, cd, cd, vp, ci, vp, ci, vp]
     lib.ecwam_hip_current2wam.argtypes = [vp, ci, ci, vp, vp, cd, cd, vp, vp, vp, vp]
+    for name in EXPORTS_RESTART:
+        getattr(lib, name).restype = C.c_int
+    lib.ecwam_hip_depthprpt.argtypes = [vp, ci, ci, vp, C.POINTER(DepthOpts), vp, vp, vp, vp, vp, vp]
+    lib.ecwam_hip_buildstress.argtypes = [vp, ci, ci, vp, vp, cd, ci, cd, cd, vp, vp]
+    lib.ecwam_hip_set_restart_map.argtypes = [vp, ci, vp]
+    lib.ecwam_hip_savstress_pack.argtypes = [vp, ci, ci, vp, vp, vp, ci, vp, ci, vp]
+    lib.ecwam_hip_getstress_unpack.argtypes = [vp, ci, ci, vp, ci, ci, vp, vp, vp, vp]
+    lib.ecwam_hip_savspec_pack.argtypes = [vp, ci, ci, vp, ci, ci, ci, vp, ci, vp]
     _lib = lib
     return lib
 

@@ -103,3 +103,55 @@ def read_record(path: str, record: int = 0, dtype=np.uint8) -> np.ndarray:
                 raise EOFError(f"{path}: record {record} is cut short")
             off += ln
     return raw.view(dt)
+
+
+def write_record(path: str, data: np.ndarray, append: bool = False) -> None:
+    """One unformatted sequential record from a flat array, as the array holds it: the counterpart of read_record (the framing of write_fl,
+    sub-records included, without its transposition).  With `append` the record follows what the file holds."""
+    raw = np.ascontiguousarray(data).reshape(-1).view(np.uint8)
+    nb = raw.size
+    with open(path, "ab" if append else "wb") as f:
+        off, first = 0, True
+        while True:
+            ln = min(_MAX_SUB, nb - off)
+            last = off + ln >= nb
+            f.write(np.array([ln if last else -ln], dtype="<i4").tobytes())
+            f.write(memoryview(raw[off:off + ln]))
+            f.write(np.array([ln if first else -ln], dtype="<i4").tobytes())
+            off += ln
+            first = False
+            if last:
+                break
+
+
+NRESTART_FIELDS = 16      # savstress.F90:112-127
+_DATE_LEN = 14
+
+
+def write_stress(path: str, dates, rfield: np.ndarray) -> None:
+    """The LAW file of WRITESTRESS (writestress.F90:88-107): record 1 holds CDTPRO, CDATEWO, CDAWIFL, CDATEFL (14 characters each), then one record
+    of n reals per restart field.  rfield: [16][n] in the working precision, already in the order of the file (ecwam_hip_savstress_pack relabels)."""
+    a = np.asarray(rfield)
+    if a.ndim != 2 or a.shape[0] != NRESTART_FIELDS:
+        raise ValueError("write_stress: rfield is [16][n]")
+    if len(dates) != 4:
+        raise ValueError("write_stress: four dates (CDTPRO, CDATEWO, CDAWIFL, CDATEFL)")
+    head = b"".join(str(d).encode("ascii").ljust(_DATE_LEN)[:_DATE_LEN] for d in dates)
+    write_record(path, np.frombuffer(head, np.uint8))
+    for f in range(NRESTART_FIELDS):
+        write_record(path, a[f], append=True)
+
+
+def read_stress(path: str, n: int, dtype=np.float32):
+    """(dates, rfield [16][n]) of a LAW file, as READSTRESS reads it without relabelling (readstress.F90:99-115)."""
+    head = read_record(path, 0)
+    if head.size != 4 * _DATE_LEN:
+        raise ValueError(f"{path}: record 1 holds {head.size} bytes, expected the four dates of {_DATE_LEN} characters")
+    dates = [head[i * _DATE_LEN:(i + 1) * _DATE_LEN].tobytes().decode("ascii") for i in range(4)]
+    out = np.empty((NRESTART_FIELDS, n), np.dtype(dtype))
+    for f in range(NRESTART_FIELDS):
+        rec = read_record(path, 1 + f, dtype)
+        if rec.size != n:
+            raise ValueError(f"{path}: field {f + 1} holds {rec.size} reals, expected {n}")
+        out[f] = rec
+    return dates, out

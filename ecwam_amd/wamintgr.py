@@ -174,6 +174,7 @@ class Wamintgr:
             self.g1 = torch.zeros((self.nrows, NANG, lfp), **z)
             self.g2 = torch.zeros((self.nrows, NANG, lfp), **z)
         self.weights_ready = False
+        self.relabel = False            # set_restart_map: the restart records go out in the order of a global file
         self.halo_events = None         # a list: propag() appends a (before, after) event pair around every wait for a halo exchange
         # refraction (IREFRA = 1 depth, 2 currents, 3 both): per-point THD/S0/U/V/OMDD/CURMASK instead of the reference's
         # THDD/THDC/SDOT and 21 weight arrays; PROPAGS2 rebuilds every weight on the fly
@@ -610,6 +611,90 @@ class Wamintgr:
             blk.copy_(torch.from_numpy(rec).view(nf, self.n))
             self.ctx.getspec_unpack(0, self.n, blk, self.fl1)
         self.gfast_valid = False
+
+    # ---- the start and the end of a run on the device (include/ecwam_hip_restart.h): INITDPTHFLDS, BUILDSTRESS, SAVSTRESS / GETSTRESS, WRITEFL's record
+    def initdpthflds(self, depth=None) -> None:
+        """INITDPTHFLDS on the device: wvprpt, EMAXDPT and DEPTH of ff, cgroup_ext and, with refraction, omosnh2kd_ext / wavnum_ext from the depths of
+        the owned, halo and land rows.  depth: a device vector [nrows] (the land slot is set to BATHYMAX here), or None: the depths the model holds
+        (depth_ext with refraction, otherwise DEPTH of ff for the owned rows; then the halo rows keep the cgroup_ext they have)."""
+        n, nland = self.n, self.dom.nland
+        rows = self.nrows
+        if depth is None and not hasattr(self, "cgroup_ext"):
+            raise RuntimeError("initdpthflds() without depths recomputes what the model holds: call init_synthetic() first, or pass the depths")
+        if not hasattr(self, "cgroup_ext"):      # the depths of every row are given: nothing is kept from an earlier state
+            self.cgroup_ext = torch.empty((self.nrows, self.cfg.nfre), dtype=self.dtype, device=self.dev)
+        if depth is None:
+            if self.irefra:
+                depth = self.depth_ext.clone()
+            else:
+                depth = torch.empty(self.nrows, dtype=self.dtype, device=self.dev)
+                depth[:n] = self.ff[:, 15]
+                rows = n      # the depths of the halo rows are not kept without refraction
+        else:
+            depth = torch.as_tensor(depth, dtype=self.dtype, device=self.dev).clone()
+        if depth.shape != (self.nrows,):
+            raise ValueError(f"initdpthflds: depth is [{self.nrows}] (owned, halo and land rows)")
+        depth[nland] = float(self.t.BATHYMAX)
+        om, wn = (self.omosnh2kd_ext, self.wavnum_ext) if self.irefra else (None, None)
+        self.ctx.depthprpt(0, n, depth, wvprpt=self.wvprpt, wavnum=wn, cgroup=self.cgroup_ext, omosnh2kd=om, ff=self.ff)
+        if rows > n:
+            self.ctx.depthprpt(n, rows, depth, wavnum=wn, cgroup=self.cgroup_ext, omosnh2kd=om)
+        elif nland >= n:
+            self.ctx.depthprpt(nland, nland + 1, depth, wavnum=wn, cgroup=self.cgroup_ext, omosnh2kd=om)
+        if self.irefra:
+            self.depth_ext.copy_(depth)
+        self.weights_ready = False
+
+    def buildstress(self, uwave=None, cd=None, zref: float | None = None, nsestart: bool = False, prchar: float = 0.0185, zmiss: float = -999.0) -> None:
+        """What GETSTRESS runs for a GRIB or noise start: Z0B = 0, BUILDSTRESS from WSWAVE / WDWAVE of ff and the planes uwave / cd [ncell_in]
+        (or None), then the reset of a noise start."""
+        self.ctx.buildstress(0, self.n, self.ff, uwave, cd, zref, True, nsestart, prchar, zmiss)
+
+    def set_restart_map(self, ij2newij) -> None:
+        """IJ2NEWIJ for the owned rows, 0-based (None removes it): savstress / write_restart_device then write in the global order."""
+        if ij2newij is not None and np.asarray(ij2newij).size != self.n:
+            raise ValueError(f"restart map: one entry per owned row ({self.n})")
+        self.ctx.set_restart_map(ij2newij)
+        self.relabel = ij2newij is not None
+
+    def savstress(self) -> torch.Tensor:
+        """The sixteen restart fields of SAVSTRESS as a device tensor [16][n], relabelled when a restart map is set."""
+        u, v = self._currents()
+        rfield = torch.empty((16, self.n), dtype=self.dtype, device=self.dev)
+        self.ctx.savstress_pack(0, self.n, self.ff, u, v, rfield, self.relabel)
+        return rfield
+
+    def getstress(self, rfield) -> None:
+        """GETSTRESS's binary restart (getstress.F90:95-97, 150-165, 188-191): Z0B = 0 is overwritten by field 7; FF_NOW and the currents from rfield
+        [16][n]; with refraction the weights are built again."""
+        u, v = self._currents()
+        r = torch.as_tensor(rfield, dtype=self.dtype, device=self.dev).contiguous()
+        self.ctx.getstress_unpack(0, self.n, r, self.ff, u, v, self.relabel)
+        if self.irefra:
+            self.weights_ready = False
+
+    def write_restart_device(self, path: str, stress_path: str | None = None, dates=None) -> None:
+        """write_restart without a transposition on the host: ecwam_hip_savspec_pack forms WRITEFL's record in the storage of FL3 (as
+        read_restart_device stages it) and the field vectors are copied back as the file holds them.  stress_path: the LAW file of SAVSTRESS as
+        well, with the four dates (CDTPRO, CDATEWO, CDAWIFL, CDATEFL).  The same bytes as write_restart without a restart map."""
+        from . import restart
+        nf = self.cfg.nang * self.cfg.nfre
+        if self.n:
+            blk = self.fl3.view(-1)[: self.n * nf].view(nf, self.n)
+            self.ctx.savspec_pack(0, self.n, self.fl1, blk, 0, self.relabel)
+            rec = blk.cpu().numpy()
+        else:
+            rec = np.empty(0, self.npdt)
+        restart.write_record(path, rec)
+        if stress_path is not None:
+            restart.write_stress(stress_path, dates if dates is not None else [" " * 14] * 4, self.savstress().cpu().numpy())
+
+    def read_stress_device(self, path: str):
+        """The LAW file into FF_NOW and the currents through ecwam_hip_getstress_unpack; returns the four dates."""
+        from . import restart
+        dates, rfield = restart.read_stress(path, self.n, self.npdt)
+        self.getstress(torch.from_numpy(rfield).to(self.dev))
+        return dates
 
     def getspec(self, values, fields=None, unscale: bool = True, nfre_red: int | None = None, opts=None) -> None:
         """GETSPEC's GRIB read on one task (getspec.F90:396-660) from decoded vectors: values is one slab [nfld][NTENCODE] of the fields
