@@ -10,6 +10,25 @@ oracle/ref_stubs.F90; oracle/ref_driver.F90 is the BIND(C) layer oracle/referenc
 The tree is found from ECWAM_REFERENCE_PATH, else from "reference_path" of BASELINE.json.  Where it does not exist nothing is built and
 one line says so; where it exists a failure to compile is fatal.  Flags: -O2 -ffp-contract=off, no fast-math: the order of operations
 of the source, which is what the oracle (oracle/Makefile) restates.
+
+build_driver() builds the executables of the fixture drivers (tools/*_driver.F90, run by tools/make_golden_*.py) by the same recipe, in a
+temporary directory: it is the one place that invokes the compiler for them.  A driver USEs the reference's real modules and restates none.
+The rule: a driver holds a module of its own only where the reference's names another package, where the fake is the point of the driver,
+or where a fixture cannot be recorded with the reference's (a finding about the recorded case; the fixture stays).  The survivors:
+
+  module            driver    why
+  YOWGRIB           readwind  the point of the driver: answers GRIB2WGRID's keys from a table in place of the GRIB decoder
+  YOWGRIB           intake    the reference's is bound to GRIB_API; INITIALINT imports one name and calls nothing
+  YOWGRIB           gribout   the same: WGRIBENCODE_VALUES imports three names it does not use on this path
+  OML_MOD           gribout   another package (fiat); one name, used by this driver alone
+  MPL_MODULE        intake    another package (fiat); one name (MPL_COMM), used by this driver alone
+  MPL_DATA_MODULE   intake    the same
+  YOWWIND           forcing   the reference's RWFAC is a PARAMETER (0.5); the recorded GETWND cases weigh the current with 1 and 0.625
+  YOWPCONS          intake    the reference's WSTAR0 is a PARAMETER (0); the recorded INIT_FIELDG call sets 0.0625
+
+Two procedures are a driver's own as well, external ones whose interface header is cut from the driver: IWAM_GET_UNIT (restart: opens the
+file in the machine's byte order) and OUTMDLDCP (intake: never reached).  YOWUNBLKRORD (restart) and YOWPD (intake) are named in `standins`
+without a module behind them: the routines name them only behind WAM_HAVE_UNWAM, which is not defined.
 """
 from __future__ import annotations
 
@@ -182,13 +201,15 @@ _USE = re.compile(r"^\s*USE\s*(?:,\s*INTRINSIC\s*)?(?:::)?\s*(\w+)", re.I | re.M
 _STANDINS = {"PARKIND1", "YOMHOOK", "EC_LUN", "FIELD_MODULE", "YOWDRVTYPE", "REF_DRIVER_MOD", "REF_ADVECTION_MOD", "ISO_C_BINDING", "ISO_FORTRAN_ENV", "IEEE_ARITHMETIC"}
 
 
-def _uses(path: str) -> set[str]:
+def _uses(path: str, standins: frozenset[str] = frozenset()) -> set[str]:
     with open(path, errors="replace") as fh:
-        return {m.upper() for m in _USE.findall(fh.read())} - _STANDINS
+        return {m.upper() for m in _USE.findall(fh.read())} - _STANDINS - standins
 
 
-def module_order(src: str, files: list[str]) -> list[str]:
-    """The reference's module files (src/ecwam/<module>.F90) that `files` need, each after the modules it uses."""
+def module_order(src: str, files: list[str], standins=()) -> list[str]:
+    """The reference's module files (src/ecwam/<module>.F90) that `files` need, each after the modules it uses.  `standins` are modules the
+    caller supplies itself (or that only a branch the preprocessor drops names): they are not looked for in the tree."""
+    standins = frozenset(m.upper() for m in standins)
     order: list[str] = []
     seen: set[str] = set()
 
@@ -199,12 +220,12 @@ def module_order(src: str, files: list[str]) -> list[str]:
         p = os.path.join(src, mod.lower() + ".F90")
         if not os.path.exists(p):
             raise RuntimeError(f"reference module {mod} not found at {p}")
-        for d in sorted(_uses(p)):
+        for d in sorted(_uses(p, standins)):
             visit(d)
         order.append(p)
 
     for f in files:
-        for d in sorted(_uses(f)):
+        for d in sorted(_uses(f, standins)):
             visit(d)
     return order
 
@@ -214,6 +235,22 @@ def _compile(src: str, obj: str, flags: list[str]) -> None:
     r = subprocess.run([FLANG, *flags, "-c", src, "-o", obj], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     if r.returncode:
         raise RuntimeError(f"reference build: flang failed for {src}:\n{r.stdout[-4000:]}")
+
+
+def _includes(files: list[str]) -> set[str]:
+    """The <routine>.intfb.h that `files` include."""
+    names: set[str] = set()
+    for f in files:
+        with open(f, errors="replace") as fh:
+            names.update(re.findall(r'^#include\s+"(\w+\.intfb\.h)"', fh.read(), re.M))
+    return names
+
+
+def _empty_headers(files: list[str], hdr: str, src: str) -> None:
+    """Headers of routines of other packages (fiat's ABOR1 ...) that `files` include: empty, the stand-ins have explicit-shape dummies."""
+    for h in _includes(files):
+        if not os.path.exists(os.path.join(hdr, h)) and not os.path.exists(os.path.join(src, h)):
+            open(os.path.join(hdr, h), "w").close()
 
 
 def _stale(ref: str) -> bool:
@@ -248,11 +285,7 @@ def build(force: bool = False) -> bool:
         raise RuntimeError(f"reference build: not in the tree: {missing}")
     ours = [os.path.join(_HERE, f) for f in OURS]
     mods = module_order(src, routines + ours[1:])
-    for f in routines + mods:      # headers of routines of other packages (fiat's ABOR1 ...): empty, the stand-ins have explicit-shape dummies
-        with open(f, errors="replace") as fh:
-            for h in re.findall(r'^#include\s+"(\w+\.intfb\.h)"', fh.read(), re.M):
-                if not os.path.exists(os.path.join(hdr, h)) and not os.path.exists(os.path.join(src, h)):
-                    open(os.path.join(hdr, h), "w").close()
+    _empty_headers(routines + mods, hdr, src)
     for prec in ("dp", "sp"):
         d = os.path.join(OUT, prec)
         shutil.rmtree(d, ignore_errors=True)
@@ -277,6 +310,76 @@ def build(force: bool = False) -> bool:
             raise RuntimeError(f"reference build: link failed:\n{r.stdout[-4000:]}")
         os.replace(tmp, lib_path(prec))
     return True
+
+
+# ---- fixture drivers -----------------------------------------------------------------------------------------------------------------
+def _external_units(text: str) -> dict[str, str]:
+    """The external procedures of a driver (the program units that are neither its modules nor its program), by name: the driver carries
+    the interface of a routine it supplies in place of the reference's, and its header is cut from there."""
+    units, inside, cur = {}, None, None
+    for line in text.splitlines():
+        if line.lstrip().startswith(("!", "#")):
+            continue
+        if cur is not None:
+            units[cur] += line + "\n"
+            if re.match(rf"\s*END\s+(SUBROUTINE|FUNCTION)\s+{cur}\b", line, re.I):
+                cur = None
+        elif inside:
+            inside = not re.match(r"\s*END\s+(MODULE|PROGRAM)\b", line, re.I)
+        elif re.match(r"\s*(MODULE|PROGRAM)\s+\w+", line, re.I):
+            inside = True
+        elif _UNIT.match(line):
+            cur = _UNIT.match(line).group("name")
+            units[cur] = line + "\n"
+    return units
+
+
+def build_driver(driver_src: str, routines, workdir: str, precision: str, standins=(), flags=(), ref: str | None = None) -> str:
+    """The executable of a fixture driver (tools/*_driver.F90), built in `workdir` (outside the tree) by the recipe of build(): the stand-ins
+    of ref_stubs.F90, the reference's real modules that `routines` (names of src/ecwam/<name>.F90) and the driver use, in order, the driver,
+    the routines, and the link.  `standins` names the modules of the reference tree that are not taken from it (the table in the module
+    docstring); `flags` are the driver's own (-D..., -fopenmp).  The headers are written once per `workdir`, for both precisions: those of the
+    tree's routines, over them those of the external procedures the driver defines, and empty ones as in build()."""
+    src = os.path.join(ref or reference_root() or "", "src", "ecwam")
+    if routines and not os.path.isdir(src):
+        raise RuntimeError(f"driver build: no reference tree at {src}")
+    routines = [os.path.join(src, r + ".F90") for r in routines]
+    hdr = os.path.join(workdir, "intfb")
+    fresh = not os.path.isdir(hdr)
+    if fresh:
+        os.makedirs(hdr)
+        if os.path.isdir(src):
+            write_headers(src, hdr)
+        with open(driver_src) as fh:
+            for name, unit in _external_units(fh.read()).items():
+                with open(os.path.join(hdr, name.lower() + ".intfb.h"), "w") as out:
+                    out.write(interface_of(unit))
+    # a header names the modules of its routine: they are built too, though the routine itself (ABORT1 ...) may not be
+    files = routines + [driver_src]
+    while True:
+        mods = module_order(src, files, standins)
+        more = [p for p in (os.path.join(hdr, h) for h in sorted(_includes(files + mods))) if os.path.exists(p) and p not in files]
+        if not more:
+            break
+        files += more
+    if fresh:
+        _empty_headers(routines + mods, hdr, src)
+    d = os.path.join(workdir, precision)
+    os.makedirs(d)
+    # FLAGS without -fPIC (an executable, as the fixtures were recorded); -fopenmp, where a driver asks for it, goes to the link as well
+    flags = [f for f in FLAGS if f != "-fPIC"] + ["-module-dir", d, "-I", d, "-I", hdr, "-I", src, *flags] + (["-DREF_SINGLE"] if precision == "sp" else [])
+    # the driver before the routines: where it supplies a module (YOWGRIB ...), the routines use it
+    first = [os.path.join(_HERE, OURS[0]), *mods, driver_src]
+    objs = {p: os.path.join(d, os.path.basename(p)[:-4] + ".o") for p in first + routines}
+    for p in first:
+        _compile(p, objs[p], flags)
+    with ThreadPoolExecutor(max_workers=min(16, os.cpu_count() or 1)) as ex:
+        list(ex.map(lambda p: _compile(p, objs[p], flags), routines))
+    exe = os.path.join(d, os.path.basename(driver_src)[:-4])
+    r = subprocess.run([FLANG, *[f for f in flags if f == "-fopenmp"], "-o", exe, *objs.values()], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    if r.returncode:
+        raise RuntimeError(f"driver build: link failed:\n{r.stdout[-4000:]}")
+    return exe
 
 
 if __name__ == "__main__":

@@ -1,10 +1,12 @@
-! Driver of tools/make_golden_forcing.py: calls the reference's WAMWND, MICEP, CDUSTARZ0, WAMADSWSTAR, WAMCUR and OUTBETA, compiled unmodified
-! from the reference tree, on the records of a stream file and writes what they return.  The modules below are the stub those routines need:
-! the kinds of PARKIND_WAVE (-DSINGLE: the single precision build; JWRO is double, the kind of the library's NEMO buffer), the two derived
-! types with the members the routines name, and the members of the model's modules they use, as variables this program fills from the file
-! (so that the reference sees the constants of ecwam_amd/tables.py and tests/forcing_ref.py, the ones the device holds).  Two pieces of the seam
-! are statements inside larger routines, not routines: the NEMO currents of getcurr.F90:168-181 and the WVBLOCK fill of wavemdl.F90:757-802.
-! The program restates those few lines around the reference's OUTBETA, as the start driver restates GETSPEC's fill loop.
+! Driver of tools/make_golden_forcing.py: calls the reference's WAMWND, MICEP, CDUSTARZ0, WAMADSWSTAR, WAMCUR and OUTBETA on the records of a
+! stream file and writes what they return.  It is built by oracle/ref_build.py::build_driver: the routines and the modules they use are the
+! reference's own files, compiled unmodified in both precisions, behind the stand-ins of oracle/ref_stubs.F90 for what other packages supply.
+! The program fills the modules' variables from the file, so that the reference sees the constants of ecwam_amd/tables.py and
+! tests/forcing_ref.py, the ones the device holds; what the reference declares a PARAMETER is compared with the file's value instead.  One
+! module is the driver's own: YOWWIND, because the reference's RWFAC is a PARAMETER (0.5) and the recorded cases weigh the current with 1 and
+! 0.625.  Two pieces of the seam are statements inside larger routines, not routines: the NEMO currents of getcurr.F90:168-181 and the WVBLOCK
+! fill of wavemdl.F90:757-802.  The program restates those few lines around the reference's OUTBETA, as the start driver restates GETSPEC's
+! fill loop.
 ! Input  (stream, little endian): NPTS, NX, NY (int32); IFROMIJ(NPTS), JFROMIJ(NPTS) (int32, 1-based); then records, each led by an int32 OP
 !        (0 = the end), 24 real64 S and 16 int32 L:
 !          S = G, GM1, ZPI, EPSUS, ZMISS, XKAPPA, XNLEV, RNUM, PRCHAR, ALPHAMIN, ALPHAMAX, ALPHA, WSPMIN, RWFAC, HICMIN, CITHRSH, SWAMPCITH, CDMAX,
@@ -22,122 +24,12 @@
 !                         USTOKES, VSTOKES, PHIOCD, TAUOCXD, TAUOCYD, TAUICX, TAUICY, WSEMEAN, WSFMEAN (NPTS) -> WVBLOCK(NPTS,NWVFIELDS)
 !        Every real is representable in the working precision.
 ! Output (stream): per record the columns listed, NPTS real64 each: the working-precision results, widened.
-MODULE PARKIND_WAVE
-  IMPLICIT NONE
-  INTEGER, PARAMETER :: JWIM = SELECTED_INT_KIND(9)
-#ifdef SINGLE
-  INTEGER, PARAMETER :: JWRB = SELECTED_REAL_KIND(6, 37)
-#else
-  INTEGER, PARAMETER :: JWRB = SELECTED_REAL_KIND(13, 300)
-#endif
-  INTEGER, PARAMETER :: JWRU = SELECTED_REAL_KIND(13, 300)
-  INTEGER, PARAMETER :: JWRO = SELECTED_REAL_KIND(13, 300)
-END MODULE PARKIND_WAVE
-
-MODULE YOMHOOK
-  IMPLICIT NONE
-  INTEGER, PARAMETER :: JPHOOK = SELECTED_REAL_KIND(13, 300)
-  LOGICAL :: LHOOK = .FALSE.
-CONTAINS
-  SUBROUTINE DR_HOOK(CDNAME, KSWITCH, PKEY)
-    CHARACTER(LEN=*), INTENT(IN) :: CDNAME
-    INTEGER, INTENT(IN) :: KSWITCH
-    REAL(KIND=JPHOOK), INTENT(INOUT) :: PKEY
-  END SUBROUTINE DR_HOOK
-END MODULE YOMHOOK
-
-MODULE YOWDRVTYPE
-  USE PARKIND_WAVE, ONLY : JWIM, JWRB
-  IMPLICIT NONE
-  TYPE FORCING_FIELDS
-    REAL(KIND=JWRB), POINTER :: UWND(:,:) => NULL(), VWND(:,:) => NULL(), AIRD(:,:) => NULL(), WSTAR(:,:) => NULL(), CICOVER(:,:) => NULL(),  &
- &                              CITHICK(:,:) => NULL(), USTRA(:,:) => NULL(), VSTRA(:,:) => NULL(), WSWAVE(:,:) => NULL(), WDWAVE(:,:) => NULL(),  &
- &                              LKFR(:,:) => NULL(), UCUR(:,:) => NULL(), VCUR(:,:) => NULL()
-  END TYPE FORCING_FIELDS
-  TYPE WVGRIDLOC
-    INTEGER(KIND=JWIM), POINTER :: IFROMIJ(:,:) => NULL(), JFROMIJ(:,:) => NULL()
-  END TYPE WVGRIDLOC
-END MODULE YOWDRVTYPE
-
-MODULE YOWCOUP
-  IMPLICIT NONE
-  LOGICAL :: LWCOU, LWNEMOCOUCIC, LWNEMOCOUCIT, LLGCBZ0
-END MODULE YOWCOUP
-
-MODULE YOWPCONS
-  USE PARKIND_WAVE, ONLY : JWRB
-  IMPLICIT NONE
-  REAL(KIND=JWRB) :: G, GM1, ZPI, ZMISS, EPSUS, C1CD, C2CD, P1CD, P2CD, CDMAX
-END MODULE YOWPCONS
-
-MODULE YOWPHYS
-  USE PARKIND_WAVE, ONLY : JWRB
-  IMPLICIT NONE
-  REAL(KIND=JWRB) :: XKAPPA, XNLEV, RNUM, PRCHAR, ALPHAMIN, ALPHAMAX, ALPHA
-END MODULE YOWPHYS
-
-MODULE YOWSTAT
-  USE PARKIND_WAVE, ONLY : JWIM
-  IMPLICIT NONE
-  INTEGER(KIND=JWIM) :: IREFRA
-  LOGICAL :: LRELWIND
-END MODULE YOWSTAT
-
-MODULE YOWTEST
-  USE PARKIND_WAVE, ONLY : JWIM
-  IMPLICIT NONE
-  INTEGER(KIND=JWIM) :: IU06 = 6
-END MODULE YOWTEST
-
 MODULE YOWWIND
   USE PARKIND_WAVE, ONLY : JWRB
   IMPLICIT NONE
   REAL(KIND=JWRB) :: WSPMIN, RWFAC
   LOGICAL :: LLWSWAVE, LLWDWAVE
 END MODULE YOWWIND
-
-MODULE YOWICE
-  USE PARKIND_WAVE, ONLY : JWRB
-  IMPLICIT NONE
-  REAL(KIND=JWRB) :: CITHRSH, HICMIN
-  LOGICAL :: LICERUN, LMASKICE, LICETH, LCIWA1 = .FALSE.
-END MODULE YOWICE
-
-MODULE YOWMAP
-  USE PARKIND_WAVE, ONLY : JWIM
-  IMPLICIT NONE
-  INTEGER(KIND=JWIM) :: NGX, NGY
-  CHARACTER(LEN=1) :: CLDOMAIN = 'g'
-END MODULE YOWMAP
-
-MODULE YOWMPP
-  USE PARKIND_WAVE, ONLY : JWIM
-  IMPLICIT NONE
-  INTEGER(KIND=JWIM) :: IRANK = 1, NPROC = 1
-END MODULE YOWMPP
-
-MODULE YOWPARAM
-  USE PARKIND_WAVE, ONLY : JWRB
-  IMPLICIT NONE
-  REAL(KIND=JWRB) :: SWAMPCITH
-END MODULE YOWPARAM
-
-MODULE YOWNEMOFLDS
-  IMPLICIT NONE
-  LOGICAL :: LNEMOICEREST
-END MODULE YOWNEMOFLDS
-
-MODULE YOWCURR
-  USE PARKIND_WAVE, ONLY : JWRB
-  IMPLICIT NONE
-  REAL(KIND=JWRB) :: CURRENT_MAX
-END MODULE YOWCURR
-
-MODULE YOWGRID
-  USE PARKIND_WAVE, ONLY : JWIM
-  IMPLICIT NONE
-  INTEGER(KIND=JWIM) :: NPROMA_WAM, NCHNK
-END MODULE YOWGRID
 
 PROGRAM FORCING_DRIVER
   USE PARKIND_WAVE, ONLY : JWIM, JWRB, JWRO
@@ -147,22 +39,15 @@ PROGRAM FORCING_DRIVER
   USE YOWPHYS, ONLY : XKAPPA, XNLEV, RNUM, PRCHAR, ALPHAMIN, ALPHAMAX, ALPHA
   USE YOWSTAT, ONLY : IREFRA, LRELWIND
   USE YOWWIND, ONLY : WSPMIN, RWFAC, LLWSWAVE, LLWDWAVE
-  USE YOWICE, ONLY : CITHRSH, HICMIN, LICERUN, LMASKICE, LICETH
+  USE YOWICE, ONLY : CITHRSH, HICMIN, LICERUN, LMASKICE, LICETH, LCIWA1
   USE YOWMAP, ONLY : NGX, NGY, CLDOMAIN
   USE YOWPARAM, ONLY : SWAMPCITH
   USE YOWNEMOFLDS, ONLY : LNEMOICEREST
   USE YOWCURR, ONLY : CURRENT_MAX
   USE YOWGRID, ONLY : NPROMA_WAM, NCHNK
+  USE YOWMPP, ONLY : IRANK, NPROC
   IMPLICIT NONE
-  INTERFACE      ! OUTBETA has an optional argument: its caller needs the interface
-    SUBROUTINE OUTBETA(KIJS, KIJL, U10, USTAR, Z0M, Z0B, CHRNCK, BETAM, BETAHQ, CD)
-      USE PARKIND_WAVE, ONLY : JWIM, JWRB
-      INTEGER(KIND=JWIM), INTENT(IN) :: KIJS, KIJL
-      REAL(KIND=JWRB), DIMENSION(KIJL), INTENT(IN) :: U10, USTAR, Z0M, Z0B, CHRNCK
-      REAL(KIND=JWRB), DIMENSION(KIJL), INTENT(OUT) :: BETAM, BETAHQ
-      REAL(KIND=JWRB), DIMENSION(KIJL), INTENT(OUT), OPTIONAL :: CD
-    END SUBROUTINE OUTBETA
-  END INTERFACE
+#include "outbeta.intfb.h"
   INTEGER, PARAMETER :: R8 = SELECTED_REAL_KIND(13, 300)
   INTEGER(KIND=JWIM) :: NPTS, NX, NY, OP, L(16), FL(5), ICODE_WND, IPARAMCI, NWV, IJ, IX, JY, IFLD, J
   LOGICAL :: LWCUR, LWCOU2W, LWCOUHMF, LWSTOKES, LWFLUX
@@ -189,6 +74,9 @@ PROGRAM FORCING_DRIVER
   NGY = NY
   NPROMA_WAM = NPTS
   NCHNK = 1
+  IRANK = 1
+  NPROC = 1
+  LCIWA1 = .FALSE.
   FIELDG%UWND => GF(:,:,1)
   FIELDG%VWND => GF(:,:,2)
   FIELDG%AIRD => GF(:,:,3)
@@ -213,26 +101,26 @@ PROGRAM FORCING_DRIVER
     G = REAL(S(1), JWRB)
     GM1 = REAL(S(2), JWRB)
     ZPI = REAL(S(3), JWRB)
-    EPSUS = REAL(S(4), JWRB)
+    IF (REAL(S(4), JWRB) /= EPSUS) ERROR STOP 'EPSUS'
     ZMISS = REAL(S(5), JWRB)
-    XKAPPA = REAL(S(6), JWRB)
-    XNLEV = REAL(S(7), JWRB)
+    IF (REAL(S(6), JWRB) /= XKAPPA) ERROR STOP 'XKAPPA'
+    IF (REAL(S(7), JWRB) /= XNLEV) ERROR STOP 'XNLEV'
     RNUM = REAL(S(8), JWRB)
     PRCHAR = REAL(S(9), JWRB)
     ALPHAMIN = REAL(S(10), JWRB)
-    ALPHAMAX = REAL(S(11), JWRB)
+    IF (REAL(S(11), JWRB) /= ALPHAMAX) ERROR STOP 'ALPHAMAX'
     ALPHA = REAL(S(12), JWRB)
     WSPMIN = REAL(S(13), JWRB)
     RWFAC = REAL(S(14), JWRB)
-    HICMIN = REAL(S(15), JWRB)
+    IF (REAL(S(15), JWRB) /= HICMIN) ERROR STOP 'HICMIN'
     CITHRSH = REAL(S(16), JWRB)
     SWAMPCITH = REAL(S(17), JWRB)
-    CDMAX = REAL(S(18), JWRB)
-    C1CD = REAL(S(19), JWRB)
-    C2CD = REAL(S(20), JWRB)
-    P1CD = REAL(S(21), JWRB)
-    P2CD = REAL(S(22), JWRB)
-    CURRENT_MAX = REAL(S(23), JWRB)
+    IF (REAL(S(18), JWRB) /= CDMAX) ERROR STOP 'CDMAX'
+    IF (REAL(S(19), JWRB) /= C1CD) ERROR STOP 'C1CD'
+    IF (REAL(S(20), JWRB) /= C2CD) ERROR STOP 'C2CD'
+    IF (REAL(S(21), JWRB) /= P1CD) ERROR STOP 'P1CD'
+    IF (REAL(S(22), JWRB) /= P2CD) ERROR STOP 'P2CD'
+    IF (REAL(S(23), JWRB) /= CURRENT_MAX) ERROR STOP 'CURRENT_MAX'
     ICODE_WND = L(1)
     LLWSWAVE = L(2) /= 0
     LLWDWAVE = L(3) /= 0

@@ -2,18 +2,13 @@
 ! (grib2wgrid.F90:771-775 the un-scaling, 793-802 the full copy into FIELD; getspec.F90:458-462 the gather, 548-552 the store with
 ! ZMISS -> EPSMIN) sit inside GRIB2WGRID and GETSPEC, which are bound to eccodes and MPL and do not compile alone.  This program is the project's
 ! own few lines around Fortran's own `**`: what it pins is the compiler's evaluation of 10**(V - |PPREC|) - PPEPS in the working precision
-! (-DSINGLE: single), through a two-dimensional FIELD as the reference goes, not a compiled reference routine.
+! (both are built, by oracle/ref_build.py::build_driver as every driver is), through a two-dimensional FIELD as the reference goes, not a compiled reference routine.
 ! Input  (stream, little endian): NGX, NGY, NPTS, NVAL, NFLD, IUNSCALE (int32); PPEPS, PPREC, ZMISS, EPSMIN (real64); NLONRGG(NGY), IXLG(NPTS),
 !        KXLT(NPTS) (int32); V8(NVAL,NFLD) (real64), the decoded vectors.  Every real is representable in the working precision.
 ! Output (stream): FL(NPTS) per field (real64): the working-precision result, widened.
 PROGRAM GRIBIN_DRIVER
+  USE PARKIND1, ONLY : JWIM => JPIM, JWRB => JPRB      ! oracle/ref_stubs.F90: the kinds parkind_wave.F90 takes (-DREF_SINGLE: single)
   IMPLICIT NONE
-  INTEGER, PARAMETER :: JWIM = SELECTED_INT_KIND(9)
-#ifdef SINGLE
-  INTEGER, PARAMETER :: JWRB = SELECTED_REAL_KIND(6, 37)
-#else
-  INTEGER, PARAMETER :: JWRB = SELECTED_REAL_KIND(13, 300)
-#endif
   INTEGER(KIND=JWIM) :: H(6), NGX, NGY, NPTS, NVAL, NFLD, IUNSCALE, IFLD, IJ, J, I, L
   REAL(KIND=8) :: R(4)
   REAL(KIND=JWRB) :: PPEPS, PPREC, ZMISS, EPSMIN

@@ -1,7 +1,9 @@
-! Driver of tools/make_golden_gribout.py: calls the reference's WGRIBENCODE_VALUES, compiled unmodified from the reference tree, on the fields of a
-! stream file and writes the vector VALUES it returns.  The modules below are the stubs the routine needs: the kinds of PARKIND_WAVE (-DSINGLE:
-! the single precision build) and the names it imports without using them on this path.  Build with -fopenmp: the routine declares
-! OMP_GET_MAX_THREADS behind an OpenMP sentinel; its result does not depend on the number of threads (a maximum over chunks).
+! Driver of tools/make_golden_gribout.py: calls the reference's WGRIBENCODE_VALUES on the fields of a stream file and writes the vector VALUES it
+! returns.  It is built by oracle/ref_build.py::build_driver: the routine, PARKIND_WAVE and YOWGRIBHD are the reference's own files, compiled
+! unmodified in both precisions, behind the stand-ins of oracle/ref_stubs.F90 for what other packages supply.  Two modules are the driver's own,
+! each the names the routine imports without using them on this path: YOWGRIB (the reference's is bound to the GRIB decoder) and OML_MOD (another
+! package).  Built with -fopenmp: the routine declares OMP_GET_MAX_THREADS behind an OpenMP sentinel; its result does not depend on the number
+! of threads (a maximum over chunks).
 ! Around the call the program restates the few statements of the callers that the routine takes for granted:
 !   outspec.F90:96-118    the sea-ice mask  SPEC = (1 - ZMASK) FL1 + ZMASK FLMIN,  ZMASK = CICOVER > CITHRSH
 !   outwspec.F90:124      FIELD(:,:) = ZMISS          (makegrid.F90:105-109 does the same)
@@ -10,45 +12,11 @@
 !        AMONOP, AMOSOP, XDELLA, PPMISS, PPEPS, PPREC, PPRESOL, PPMIN_RESET, ZMISS, CITHRSH, FLMIN (real64); NLONRGG(NGY), IXLG(NPTS), KXLT(NPTS)
 !        (int32); CICOVER(NPTS), BLOCK(NPTS,NFLD) (real64).  Every real is representable in the working precision.
 ! Output (stream): VALUES(NTENCODE) per field (real64): the working-precision result, widened.
-MODULE PARKIND_WAVE
-  IMPLICIT NONE
-  INTEGER, PARAMETER :: JWIM = SELECTED_INT_KIND(9)
-#ifdef SINGLE
-  INTEGER, PARAMETER :: JWRB = SELECTED_REAL_KIND(6, 37)
-#else
-  INTEGER, PARAMETER :: JWRB = SELECTED_REAL_KIND(13, 300)
-#endif
-  INTEGER, PARAMETER :: JWRU = SELECTED_REAL_KIND(13, 300)
-END MODULE PARKIND_WAVE
-
-MODULE YOWGRIBHD
-  IMPLICIT NONE
-  INTEGER :: NTRG2TMPD = 0, NTRG2TMPP = 0
-  LOGICAL :: LLRSTGRIBPARAM = .FALSE.
-END MODULE YOWGRIBHD
-
 MODULE YOWGRIB
   IMPLICIT NONE
   INTEGER, PARAMETER :: JPGRIB_SUCCESS = 0
   INTEGER :: IGRIB_GET_VALUE = 0, IGRIB_SET_VALUE = 0
 END MODULE YOWGRIB
-
-MODULE YOMHOOK
-  IMPLICIT NONE
-  INTEGER, PARAMETER :: JPHOOK = SELECTED_REAL_KIND(13, 300)
-  LOGICAL :: LHOOK = .FALSE.
-CONTAINS
-  SUBROUTINE DR_HOOK(CDNAME, KSWITCH, PKEY)
-    CHARACTER(LEN=*), INTENT(IN) :: CDNAME
-    INTEGER, INTENT(IN) :: KSWITCH
-    REAL(KIND=JPHOOK), INTENT(INOUT) :: PKEY
-  END SUBROUTINE DR_HOOK
-END MODULE YOMHOOK
-
-MODULE EC_LUN
-  IMPLICIT NONE
-  INTEGER, PARAMETER :: NULERR = 0
-END MODULE EC_LUN
 
 MODULE OML_MOD
   IMPLICIT NONE
@@ -57,28 +25,9 @@ END MODULE OML_MOD
 
 PROGRAM GRIBOUT_DRIVER
   USE PARKIND_WAVE, ONLY : JWIM, JWRB
+  USE YOWGRIBHD, ONLY : LLRSTGRIBPARAM
   IMPLICIT NONE
-  ! VALUES is assumed-shape: the call needs an explicit interface
-  INTERFACE
-    SUBROUTINE WGRIBENCODE_VALUES(I1, I2, FIELD, ITABPAR, LLSPECNOT251, PPMISS, PPEPS, PPREC, PPRESOL, PPMIN_RESET, NTENCODE, NGRBRESS, LPADPOLES, &
- &                                NLONRGG_SIZE, NLONRGG, IRGG, AMONOP, AMOSOP, XDELLA, CLDOMAIN, ZMISS, VALUES)
-      USE PARKIND_WAVE, ONLY : JWIM, JWRB
-      INTEGER(KIND=JWIM), INTENT(IN) :: I1, I2
-      REAL(KIND=JWRB), INTENT(INOUT) :: FIELD(I1,I2)
-      INTEGER(KIND=JWIM), INTENT(IN) :: ITABPAR
-      LOGICAL, INTENT(IN) :: LLSPECNOT251
-      REAL(KIND=JWRB), INTENT(IN) :: PPMISS, PPEPS, PPREC, PPRESOL, PPMIN_RESET
-      INTEGER(KIND=JWIM), INTENT(IN) :: NTENCODE, NGRBRESS
-      LOGICAL, INTENT(IN) :: LPADPOLES
-      INTEGER(KIND=JWIM), INTENT(IN) :: NLONRGG_SIZE
-      INTEGER(KIND=JWIM), INTENT(IN) :: NLONRGG(NLONRGG_SIZE)
-      INTEGER(KIND=JWIM), INTENT(IN) :: IRGG
-      REAL(KIND=JWRB), INTENT(IN) :: AMONOP, AMOSOP, XDELLA
-      CHARACTER(LEN=1), INTENT(IN) :: CLDOMAIN
-      REAL(KIND=JWRB), INTENT(IN) :: ZMISS
-      REAL(KIND=JWRB), DIMENSION(:), INTENT(INOUT) :: VALUES
-    END SUBROUTINE WGRIBENCODE_VALUES
-  END INTERFACE
+#include "wgribencode_values.intfb.h"
 
   INTEGER(KIND=JWIM) :: H(11), NGX, NGY, NPTS, IRGG, NTENCODE, NFLD, ITABPAR, ICE, NGRBRESS, IJ, IX, IY, IFLD
   LOGICAL :: LPADPOLES
@@ -90,6 +39,7 @@ PROGRAM GRIBOUT_DRIVER
   REAL(KIND=JWRB), ALLOCATABLE :: ZMASK(:), SPEC(:), FIELD(:,:), VALUES(:)
   CHARACTER(LEN=512) :: FIN, FOUT
 
+  LLRSTGRIBPARAM = .FALSE.
   CALL GET_COMMAND_ARGUMENT(1, FIN)
   CALL GET_COMMAND_ARGUMENT(2, FOUT)
   OPEN(11, FILE=TRIM(FIN), ACCESS='STREAM', FORM='UNFORMATTED', STATUS='OLD')

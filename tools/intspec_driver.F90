@@ -1,28 +1,13 @@
-! Driver of tools/make_golden_nest.py: calls the reference's INTSPEC (with its ROTSPEC and STRSPEC, compiled unmodified from the reference
-! tree) on the cases of a stream file and writes what it returns.  The two modules below are the stub the three routines need: the kinds
-! of PARKIND_WAVE (-DSINGLE: the single precision build) and ZPI of YOWPCONS as the model sets it (2 PI, PI = 4 ATAN(1)).
+! Driver of tools/make_golden_nest.py: calls the reference's INTSPEC (with its ROTSPEC and STRSPEC) on the cases of a stream file and writes
+! what it returns.  It is built by oracle/ref_build.py::build_driver: the three routines, PARKIND_WAVE and YOWPCONS are the reference's own
+! files, compiled unmodified in both precisions; the driver holds no module of its own.  The program sets ZPI of YOWPCONS as the model does
+! (2 PI, PI = 4 ATAN(1)).
 ! Input  (stream, little endian): NCASE, NANG, NFRE (int32); FR(NFRE) (real64); per case DEL1L, FMEAN1, EMEAN1, THETM1, FMEAN2, EMEAN2,
 !        THETM2 (real64), F1(NANG,NFRE), F2(NANG,NFRE) (real64).  Every value is representable in the working precision.
 ! Output (stream): per case FMEAN, EMEAN, THETM (real64), FL(NANG,NFRE) (real64): the working-precision results, widened.
-MODULE PARKIND_WAVE
-  IMPLICIT NONE
-  INTEGER, PARAMETER :: JWIM = SELECTED_INT_KIND(9)
-#ifdef SINGLE
-  INTEGER, PARAMETER :: JWRB = SELECTED_REAL_KIND(6, 37)
-#else
-  INTEGER, PARAMETER :: JWRB = SELECTED_REAL_KIND(13, 300)
-#endif
-  INTEGER, PARAMETER :: JWRU = SELECTED_REAL_KIND(13, 300)
-END MODULE PARKIND_WAVE
-
-MODULE YOWPCONS
-  USE PARKIND_WAVE, ONLY : JWRB
-  IMPLICIT NONE
-  REAL(KIND=JWRB), PARAMETER :: ZPI = 8.0_JWRB*ATAN(1.0_JWRB)
-END MODULE YOWPCONS
-
 PROGRAM INTSPEC_DRIVER
   USE PARKIND_WAVE, ONLY : JWIM, JWRB
+  USE YOWPCONS, ONLY : ZPI
   IMPLICIT NONE
   INTEGER, PARAMETER :: R8 = SELECTED_REAL_KIND(13, 300)
   INTEGER(KIND=JWIM) :: NCASE, NANG, NFRE, IC
@@ -32,6 +17,7 @@ PROGRAM INTSPEC_DRIVER
   REAL(KIND=JWRB) :: FMEAN, EMEAN, THETM
   CHARACTER(LEN=512) :: FIN, FOUT
 
+  ZPI = 8.0_JWRB*ATAN(1.0_JWRB)
   CALL GET_COMMAND_ARGUMENT(1, FIN)
   CALL GET_COMMAND_ARGUMENT(2, FOUT)
   OPEN(11, FILE=TRIM(FIN), ACCESS='STREAM', FORM='UNFORMATTED', STATUS='OLD')

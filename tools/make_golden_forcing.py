@@ -1,6 +1,6 @@
 """Generates tests/golden/forcing_0.npz and tests/golden/forcing_observed.json by RUNNING the reference's own WAMWND, MICEP, CDUSTARZ0,
-WAMADSWSTAR, WAMCUR and OUTBETA (src/ecwam/*.F90), compiled unmodified with the ROCm flang against the stub modules of
-tools/forcing_driver.F90, in double and in single precision (-cpp -O2 -ffp-contract=off, -DSINGLE).  Everything is built in a temporary
+WAMADSWSTAR, WAMCUR and OUTBETA (src/ecwam/*.F90) behind tools/forcing_driver.F90, built by oracle/ref_build.py::build_driver with the
+reference's own modules in double and in single precision.  Everything is built in a temporary
 directory outside the tree; the reference's text is read by the compiler, never copied.  The fixtures hold outputs only: what the routines
 returned on the 64 active rows, per recorded call (tests/forcing_ref.py::CALLS) and precision; the inputs are those of
 tests/forcing_ref.py::make_cases, which the tests rebuild (float32-representable, so that both precisions see the same numbers).  Only usable
@@ -21,10 +21,8 @@ each |a - b| / max(|b|, the column's largest |b| over the points); for WDWAVE th
     python tools/make_golden_forcing.py <root of the reference tree> [<directory to write to; default tests/golden>]
 """
 import glob
-import json
 import os
 import shutil
-import subprocess
 import sys
 import tempfile
 
@@ -34,36 +32,17 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import forcing_ref as F  # noqa: E402  (the construction of the inputs and the restatement, shared with the tests)
+import golden_common as GC  # noqa: E402
 
-if len(sys.argv) < 2:
-    sys.exit(__doc__)
-REF = sys.argv[1]
-OUT = sys.argv[2] if len(sys.argv) > 2 else F.GOLDEN
-FLANG = shutil.which("amdflang") or "/opt/rocm/lib/llvm/bin/flang"
-LIMIT = 600_000
-SOURCES = ("wamwnd.F90", "micep.F90", "cdustarz0.F90", "wamadswstar.F90", "wamcur.F90", "outbeta.F90")
+REF, OUT = GC.arguments(__doc__, F.GOLDEN)
+ROUTINES = ("wamwnd", "micep", "cdustarz0", "wamadswstar", "wamcur", "outbeta")
 A = slice(F.KIJS, F.KIJL)
 N = F.KIJL - F.KIJS
 # what the driver returns for GETWND, in its order
 GETWND_OUT = ["AIRD", "WDWAVE", "CICOVER", "WSWAVE", "WSTAR", "USTRA", "VSTRA", "UFRIC", "CITHICK"]
 
 
-def build(tmp, single):
-    d = os.path.join(tmp, "sp" if single else "dp")
-    os.makedirs(d)
-    flags = ["-cpp", "-O2", "-ffp-contract=off", "-module-dir", d, "-I", d] + (["-DSINGLE"] if single else [])
-    objs = []
-    for src in [os.path.join(ROOT, "tools", "forcing_driver.F90")] + [os.path.join(REF, "src", "ecwam", n) for n in SOURCES]:
-        o = os.path.join(d, os.path.basename(src).replace(".F90", ".o"))
-        subprocess.run([FLANG, *flags, "-c", src, "-o", o], check=True)
-        objs.append(o)
-    exe = os.path.join(d, "forcing_driver")
-    subprocess.run([FLANG, "-o", exe, *objs], check=True)
-    return exe
-
-
-def _r(a):
-    return np.ascontiguousarray(np.asarray(a, "<f8")).tobytes()
+_r = GC.r
 
 
 def _head(op, call, prec, o=None):
@@ -78,12 +57,11 @@ def _head(op, call, prec, o=None):
 
 
 def run(exe, tmp, prec, cases):
-    fin, fout = os.path.join(tmp, "in.bin"), os.path.join(tmp, "out.bin")
     cell = cases["map_in"][A]
     nemo = cases["nemo"][:, A]
     ff, intf = cases["ff"][A], cases["intf"][A]
     ncols = []
-    with open(fin, "wb") as fh:
+    with open(GC.infile(tmp), "wb") as fh:
         fh.write(np.array([N, F.NX, F.NY], "<i4").tobytes())
         fh.write(np.asarray(cell % F.NX + 1, "<i4").tobytes() + np.asarray(cell // F.NX + 1, "<i4").tobytes())
         for call in F.CALLS:
@@ -113,8 +91,7 @@ def run(exe, tmp, prec, cases):
                 fh.write(_r(np.stack([ff[:, F.FF[k]] for k in ("WSWAVE", "UFRIC", "Z0M", "Z0B", "CHRNCK")] + [intf[:, F.INTF[k]] for k in F.WVB_NAMES[2:]])))
                 ncols.append(nwv)
         fh.write(np.array([0], "<i4").tobytes())
-    subprocess.run([exe, fin, fout], check=True)
-    flat = np.fromfile(fout, "<f8")
+    flat = GC.drive(exe, tmp)
     assert flat.size == N * sum(ncols), (flat.size, ncols)
     out, at = {}, 0
     for call, nc in zip(F.CALLS, ncols):
@@ -148,7 +125,8 @@ def main():
     per_call = {}
     try:
         cases = F.make_cases()
-        ref = {p: run(build(tmp, p == "sp"), tmp, p, cases) for p in ("dp", "sp")}
+        exe = GC.executables(REF, "forcing", ROUTINES, tmp, standins=("YOWWIND",))
+        ref = {p: run(exe[p], tmp, p, cases) for p in ("dp", "sp")}
     finally:
         shutil.rmtree(tmp, ignore_errors=True)
     same_branches(cases, ref)
@@ -172,15 +150,10 @@ def main():
         assert np.array_equal(arrays[f"{call}_sp"].astype(np.float64), ref["sp"][call]), call
     for old in glob.glob(os.path.join(OUT, "forcing_*.npz")):
         os.remove(old)
-    path = os.path.join(OUT, "forcing_0.npz")
-    np.savez_compressed(path, **arrays)
-    assert os.path.getsize(path) <= LIMIT, os.path.getsize(path)
-    print(path, os.path.getsize(path), "bytes")
+    GC.write_npz(OUT, "forcing_0.npz", arrays)
     obs["per_call"] = per_call
     obs["error_measure"] = "per column: |a - b| / max(|b|, the column's largest |b| over the points), the maximum over the points; WDWAVE on the circle"
-    with open(os.path.join(OUT, "forcing_observed.json"), "w") as fh:
-        json.dump(obs, fh, indent=1, sort_keys=True)
-        fh.write("\n")
+    GC.write_observed(OUT, "forcing_observed.json", obs)
 
 
 if __name__ == "__main__":

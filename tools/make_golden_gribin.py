@@ -1,5 +1,5 @@
 """Generates tests/golden/gribin_0.npz and tests/golden/gribin_observed.json: the statements of GETSPEC's GRIB read evaluated by the ROCm flang in
-double and in single precision (-cpp -O2 -ffp-contract=off, -DSINGLE).
+double and in single precision, built by oracle/ref_build.py::build_driver as every driver is.
 
 What is pinned, and what is not.  None of these statements compiles alone: the un-scaling and the full copy sit inside GRIB2WGRID
 (grib2wgrid.F90:771-775, 793-802), the gather and the store inside GETSPEC (getspec.F90:458-462, 548-552), and both routines are bound to eccodes
@@ -20,10 +20,8 @@ the observed figures the tests take their gates from, each the largest |a - b| /
 
     python tools/make_golden_gribin.py <root of the reference tree (not read)> [<directory to write to; default tests/golden>]
 """
-import json
 import os
 import shutil
-import subprocess
 import sys
 import tempfile
 
@@ -34,21 +32,9 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import gribin_ref as R  # noqa: E402  (the inputs and the restatement, shared with the tests)
 import gribout_ref as G  # noqa: E402
+import golden_common as GC  # noqa: E402
 
-if len(sys.argv) < 2:
-    sys.exit(__doc__)
-OUT = sys.argv[2] if len(sys.argv) > 2 else R.GOLDEN
-FLANG = shutil.which("amdflang") or "/opt/rocm/lib/llvm/bin/flang"
-LIMIT = 600_000
-
-
-def build(tmp, single):
-    d = os.path.join(tmp, "sp" if single else "dp")
-    os.makedirs(d)
-    exe = os.path.join(d, "gribin_driver")
-    flags = ["-cpp", "-O2", "-ffp-contract=off", "-module-dir", d] + (["-DSINGLE"] if single else [])
-    subprocess.run([FLANG, *flags, os.path.join(ROOT, "tools", "gribin_driver.F90"), "-o", exe], check=True)
-    return exe
+_, OUT = GC.arguments(__doc__, R.GOLDEN)
 
 
 def run(exe, tmp, prec, g, values):
@@ -56,16 +42,14 @@ def run(exe, tmp, prec, g, values):
     t = G.tables(prec)
     nfld, nval = values.shape
     npts = g["ixlg"].size
-    fin, fout = os.path.join(tmp, "in.bin"), os.path.join(tmp, "out.bin")
     o = G.OPTS
-    with open(fin, "wb") as fh:
+    with open(GC.infile(tmp), "wb") as fh:
         fh.write(np.array([g["ngx"], g["ngy"], npts, nval, nfld, 1], "<i4").tobytes())
         fh.write(np.array([float(t.dtype(o["ppeps"])), o["pprec"], o["zmiss"], float(t.EPSMIN)], "<f8").tobytes())
         for a in (g["nlonrgg"], g["ixlg"], g["kxlt"]):
             fh.write(np.asarray(a, "<i4").tobytes())
         fh.write(np.ascontiguousarray(values, "<f8").tobytes())      # V8(NVAL,NFLD): the value index fastest
-    subprocess.run([exe, fin, fout], check=True)
-    flat = np.fromfile(fout, "<f8")
+    flat = GC.drive(exe, tmp)
     assert flat.size == nfld * npts, (flat.size, nfld, npts)
     return flat.reshape(nfld, npts)
 
@@ -74,10 +58,8 @@ def main():
     c = G.cached_cases()
     tmp = tempfile.mkdtemp(prefix="golden_gribin_")
     try:
-        ref = {}
-        for p in ("dp", "sp"):
-            exe = build(tmp, p == "sp")
-            ref[p] = {name: run(exe, tmp, p, R.grid_of(name, c), R.inputs(name)) for name in R.NAMES}
+        exe = GC.executables(None, "gribin", (), tmp)
+        ref = {p: {name: run(exe[p], tmp, p, R.grid_of(name, c), R.inputs(name)) for name in R.NAMES} for p in ("dp", "sp")}
     finally:
         shutil.rmtree(tmp, ignore_errors=True)
     kinds = ("restatement_vs_reference_dp", "restatement_vs_reference_sp", "reference_sp_vs_dp")
@@ -103,15 +85,10 @@ def main():
             obs[k] = max(obs[k], figs[k])
         per_case[name] = figs
         print(name, " ".join(f"{k} {figs[k]:.2e}" for k in kinds), f"from missing {int(miss.sum())} of {miss.size}")
-    path = os.path.join(OUT, "gribin_0.npz")
-    np.savez_compressed(path, **arrays)
-    assert os.path.getsize(path) <= LIMIT, os.path.getsize(path)
-    print(path, os.path.getsize(path), "bytes")
+    GC.write_npz(OUT, "gribin_0.npz", arrays)
     obs["per_case"] = per_case
     obs["error_measure"] = "the largest |a - b| / (|b| + PPEPS) over the decoded FL1 elements; the elements from missing values equal EPSMIN in both"
-    with open(os.path.join(OUT, "gribin_observed.json"), "w") as fh:
-        json.dump(obs, fh, indent=1, sort_keys=True)
-        fh.write("\n")
+    GC.write_observed(OUT, "gribin_observed.json", obs)
 
 
 if __name__ == "__main__":

@@ -1,6 +1,6 @@
 """Generates tests/golden/gribout_0.npz and tests/golden/gribout_observed.json by RUNNING the reference's own WGRIBENCODE_VALUES
-(src/ecwam/wgribencode_values.F90), compiled unmodified with the ROCm flang against the stub modules of tools/gribout_driver.F90, in double and
-in single precision (-cpp -O2 -fopenmp -ffp-contract=off, -DSINGLE).  Everything is built in a temporary directory outside the tree; the
+(src/ecwam/wgribencode_values.F90) behind tools/gribout_driver.F90, built by oracle/ref_build.py::build_driver (with -fopenmp) in double and
+in single precision.  Everything is built in a temporary directory outside the tree; the
 reference's text is read by the compiler, never copied.  The driver restates the few statements of OUTSPEC, OUTWSPEC and MAKEGRID around the
 routine (the sea-ice mask, FIELD = ZMISS, the block-to-grid loop).  The fixtures hold outputs only: VALUES per recorded case
 (tests/gribout_ref.py::NAMES), field and precision, and PPMAX per field -- a local of the routine, recovered as the largest non-missing value
@@ -17,10 +17,8 @@ values of the spectral cases ("values") and the same for PPMAX ("ppmax"):
 
     python tools/make_golden_gribout.py <root of the reference tree> [<directory to write to; default tests/golden>]
 """
-import json
 import os
 import shutil
-import subprocess
 import sys
 import tempfile
 
@@ -30,28 +28,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import gribout_ref as G  # noqa: E402  (the construction of the inputs and the restatement, shared with the tests)
+import golden_common as GC  # noqa: E402
 
-if len(sys.argv) < 2:
-    sys.exit(__doc__)
-REF = sys.argv[1]
-OUT = sys.argv[2] if len(sys.argv) > 2 else G.GOLDEN
-FLANG = shutil.which("amdflang") or "/opt/rocm/lib/llvm/bin/flang"
-LIMIT = 600_000
-
-
-def build(tmp, single):
-    d = os.path.join(tmp, "sp" if single else "dp")
-    os.makedirs(d)
-    open(os.path.join(d, "abort1.intfb.h"), "w").close()      # the routine includes the interface of a routine it never calls
-    flags = ["-cpp", "-O2", "-fopenmp", "-ffp-contract=off", "-module-dir", d, "-I", d] + (["-DSINGLE"] if single else [])
-    objs = []
-    for src in (os.path.join(ROOT, "tools", "gribout_driver.F90"), os.path.join(REF, "src", "ecwam", "wgribencode_values.F90")):
-        o = os.path.join(d, os.path.basename(src).replace(".F90", ".o"))
-        subprocess.run([FLANG, *flags, "-c", src, "-o", o], check=True)
-        objs.append(o)
-    exe = os.path.join(d, "gribout_driver")
-    subprocess.run([FLANG, "-fopenmp", "-o", exe, *objs], check=True)
-    return exe
+REF, OUT = GC.arguments(__doc__, G.GOLDEN)
 
 
 def run(exe, tmp, prec, g, block, cic, ice, spectral):
@@ -59,9 +38,8 @@ def run(exe, tmp, prec, g, block, cic, ice, spectral):
     t = G.tables(prec)
     _, ntencode, _ = G.value_map(g)
     nfld, npts = block.shape
-    fin, fout = os.path.join(tmp, "in.bin"), os.path.join(tmp, "out.bin")
     o = G.OPTS
-    with open(fin, "wb") as fh:
+    with open(GC.infile(tmp), "wb") as fh:
         fh.write(np.array([g["ngx"], g["ngy"], npts, g["irgg"], ntencode, nfld, 140251 if spectral else 140229, ice, int(g["lpadpoles"]), o["ngrbress"],
                            ord(g["cldomain"])], "<i4").tobytes())
         fh.write(np.array([g["amonop"], g["amosop"], g["xdella"], o["ppmiss"], float(t.dtype(o["ppeps"])), o["pprec"], float(t.dtype(o["ppresol"])), o["ppmin_reset"],
@@ -70,8 +48,7 @@ def run(exe, tmp, prec, g, block, cic, ice, spectral):
             fh.write(np.asarray(a, "<i4").tobytes())
         fh.write(np.asarray(cic, "<f8").tobytes())
         fh.write(np.ascontiguousarray(block, "<f8").tobytes())      # BLOCK(NPTS,NFLD): the point index fastest
-    subprocess.run([exe, fin, fout], check=True, env=dict(os.environ, OMP_NUM_THREADS="4"))
-    flat = np.fromfile(fout, "<f8")
+    flat = GC.drive(exe, tmp, env=dict(os.environ, OMP_NUM_THREADS="4"))
     assert flat.size == nfld * ntencode, (flat.size, nfld, ntencode)
     return flat.reshape(nfld, ntencode)
 
@@ -91,7 +68,8 @@ def main():
     tmp = tempfile.mkdtemp(prefix="golden_gribout_")
     try:
         c = G.make_cases()
-        ref = {p: reference(build(tmp, p == "sp"), tmp, p, c) for p in ("dp", "sp")}
+        exe = GC.executables(REF, "gribout", ("wgribencode_values",), tmp, standins=("YOWGRIB", "OML_MOD"), flags=("-fopenmp",))
+        ref = {p: reference(exe[p], tmp, p, c) for p in ("dp", "sp")}
     finally:
         shutil.rmtree(tmp, ignore_errors=True)
     kinds = ("restatement_vs_reference_dp", "restatement_vs_reference_sp", "reference_sp_vs_dp")
@@ -131,15 +109,10 @@ def main():
             # what is masked, scattered or padded without arithmetic differs between the precisions by the logarithm alone
             print(name, " ".join(f"{k} {figs[k]['values']:.2e}/{figs[k]['ppmax']:.2e}" for k in kinds), f"missing {int((dp == G.ZMISS).sum())} of {dp.size}")
         per_case[name] = figs
-    path = os.path.join(OUT, "gribout_0.npz")
-    np.savez_compressed(path, **arrays)
-    assert os.path.getsize(path) <= LIMIT, os.path.getsize(path)
-    print(path, os.path.getsize(path), "bytes")
+    GC.write_npz(OUT, "gribout_0.npz", arrays)
     obs["per_case"] = per_case
     obs["error_measure"] = "the largest |a - b| on the log scale over the non-missing values of VALUES (values) and over PPMAX (ppmax); the patterns of ZMISS are equal"
-    with open(os.path.join(OUT, "gribout_observed.json"), "w") as fh:
-        json.dump(obs, fh, indent=1, sort_keys=True)
-        fh.write("\n")
+    GC.write_observed(OUT, "gribout_observed.json", obs)
 
 
 if __name__ == "__main__":

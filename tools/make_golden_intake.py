@@ -1,6 +1,6 @@
 """Generates tests/golden/intake_0.npz and tests/golden/intake_observed.json by RUNNING the reference's own INITIALINT, FLDINTER, INIT_FIELDG,
-RECVNEMOFIELDS, UPDNEMOFIELDS and UPDNEMOSTRESS (src/ecwam/*.F90), compiled unmodified with the ROCm flang against the stub modules of
-tools/intake_driver.F90, in double and in single precision (-cpp -O2 -ffp-contract=off, -DSINGLE).  Everything is built in a temporary directory
+RECVNEMOFIELDS, UPDNEMOFIELDS and UPDNEMOSTRESS (src/ecwam/*.F90) behind tools/intake_driver.F90, built by
+oracle/ref_build.py::build_driver with the reference's own modules in double and in single precision.  Everything is built in a temporary directory
 outside the tree; the reference's text is read by the compiler, never copied.  The fixture holds outputs only, per case and precision: the six
 tables of INITIALINT, FIELDG on the 64 active rows and MASK_IN per FLDINTER call, INIT_FIELDG's planes, and what RECVNEMOFIELDS and the two
 UPDNEMO routines leave; the inputs are those of tests/intake_ref.py::make_cases, which the tests rebuild (float32-representable, so that both
@@ -21,10 +21,8 @@ each |a - b| / max(|b|, the plane's largest |b| over the points).
 
     python tools/make_golden_intake.py <root of the reference tree> [<directory to write to; default tests/golden>]
 """
-import json
 import os
 import shutil
-import subprocess
 import sys
 import tempfile
 
@@ -34,54 +32,16 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import intake_ref as F  # noqa: E402  (the construction of the inputs and the restatement, shared with the tests)
+import golden_common as GC  # noqa: E402
 
-if len(sys.argv) < 2:
-    sys.exit(__doc__)
-REF = sys.argv[1]
-OUT = sys.argv[2] if len(sys.argv) > 2 else F.GOLDEN
-FLANG = shutil.which("amdflang") or "/opt/rocm/lib/llvm/bin/flang"
-LIMIT = 600_000
-SOURCES = ("initialint.F90", "fldinter.F90", "init_fieldg.F90", "recvnemofields.F90", "updnemofields.F90", "updnemostress.F90")
+REF, OUT = GC.arguments(__doc__, F.GOLDEN)
+ROUTINES = ("initialint", "fldinter", "init_fieldg", "recvnemofields", "updnemofields", "updnemostress")
+# the driver's own modules (its header says why), and YOWPD, which INIT_FIELDG names only behind WAM_HAVE_UNWAM, which is not defined
+STANDINS = ("YOWGRIB", "YOWPCONS", "MPL_MODULE", "MPL_DATA_MODULE", "YOWPD")
 A = slice(F.KIJS, F.KIJL)
 N = F.KIJL - F.KIJS
 TABS = ("dj1", "dii1", "diip1", "jj", "ii", "iip")
-OUTMDLDCP_INTFB = """INTERFACE
-  SUBROUTINE OUTMDLDCP(NEMO2WAM, WAM2NEMO, NTYPE)
-    USE PARKIND_WAVE, ONLY : JWIM
-    USE YOWDRVTYPE, ONLY : OCEAN2WAVE, WAVE2OCEAN
-    TYPE(OCEAN2WAVE), INTENT(IN), OPTIONAL :: NEMO2WAM
-    TYPE(WAVE2OCEAN), INTENT(IN), OPTIONAL :: WAM2NEMO
-    INTEGER(KIND=JWIM), INTENT(IN) :: NTYPE
-  END SUBROUTINE OUTMDLDCP
-END INTERFACE
-"""
-
-
-def build(tmp, single):
-    d = os.path.join(tmp, "sp" if single else "dp")
-    os.makedirs(d)
-    # the include files the routines name: ABORT1 takes no argument and needs no interface; OUTMDLDCP is called with keywords (behind
-    # LWNEMOCOUDEBUG, which stays false), so the stub of the driver is given the interface that allows them
-    open(os.path.join(d, "abort1.intfb.h"), "w").close()
-    with open(os.path.join(d, "outmdldcp.intfb.h"), "w") as fh:
-        fh.write(OUTMDLDCP_INTFB)
-    flags = ["-cpp", "-O2", "-ffp-contract=off", "-module-dir", d, "-I", d, '-D__FILENAME__="reference"'] + (["-DSINGLE"] if single else [])
-    objs = []
-    for src in [os.path.join(ROOT, "tools", "intake_driver.F90")] + [os.path.join(REF, "src", "ecwam", n) for n in SOURCES]:
-        o = os.path.join(d, os.path.basename(src).replace(".F90", ".o"))
-        subprocess.run([FLANG, *flags, "-c", src, "-o", o], check=True)
-        objs.append(o)
-    exe = os.path.join(d, "intake_driver")
-    subprocess.run([FLANG, "-o", exe, *objs], check=True)
-    return exe
-
-
-def _r(*a):
-    return b"".join(np.ascontiguousarray(np.asarray(x, "<f8")).tobytes() for x in a)
-
-
-def _i(*a):
-    return b"".join(np.ascontiguousarray(np.asarray(x, "<i4")).tobytes() for x in a)
+_r, _i = GC.r, GC.i
 
 
 def _fort(a):
@@ -91,11 +51,10 @@ def _fort(a):
 
 def run(exe, tmp, prec, c):
     """-> the fixture's arrays of one precision (the keys without the precision) and MASK_IN per FLDINTER call"""
-    fin, fout = os.path.join(tmp, "in.bin"), os.path.join(tmp, "out.bin")
     T = F.dtype_of(prec)
     t = F.tables(prec)
     shapes = []      # per record: the names and shapes of what it returns
-    with open(fin, "wb") as fh:
+    with open(GC.infile(tmp), "wb") as fh:
         fh.write(_i(N, F.NX, F.NY, c["ifromij"][A], c["jfromij"][A]))
         for name in F.CASES:
             g = c[name]
@@ -120,8 +79,7 @@ def run(exe, tmp, prec, c):
             fh.write(_i(5, nt) + _r(_fort(c["wam2nemo"][A])))
             shapes.append([(f"upd_{nt}_fields7", (7, N)), (f"upd_{nt}_stress6", (6, N)), (f"upd_{nt}_wam2nemo", (13, N))])
         fh.write(_i(0))
-    subprocess.run([exe, fin, fout], check=True, stdout=subprocess.DEVNULL)
-    flat = np.fromfile(fout, "<f8")
+    flat = GC.drive(exe, tmp)
     out, at = {}, 0
     for rec in shapes:
         for key, shape in rec:
@@ -186,7 +144,8 @@ def main():
     tmp = tempfile.mkdtemp(prefix="golden_intake_")
     try:
         c = F.make_cases()
-        ref = {p: run(build(tmp, p == "sp"), tmp, p, c) for p in ("dp", "sp")}
+        exe = GC.executables(REF, "intake", ROUTINES, tmp, STANDINS, ('-D__FILENAME__="reference"',))
+        ref = {p: run(exe[p], tmp, p, c) for p in ("dp", "sp")}
     finally:
         shutil.rmtree(tmp, ignore_errors=True)
     taken = margins(c, ref)
@@ -238,16 +197,11 @@ def main():
                 arrays[f"{head}_{p}_{k}"] = a
             else:
                 arrays[f"{key}_{p}"] = a
-    path = os.path.join(OUT, "intake_0.npz")
-    np.savez_compressed(path, **arrays)
-    assert os.path.getsize(path) <= LIMIT, os.path.getsize(path)
-    print(path, os.path.getsize(path), "bytes")
+    GC.write_npz(OUT, "intake_0.npz", arrays)
     obs["per_call"] = per_call
     obs["branches"] = sorted(taken)
     obs["error_measure"] = "per plane: |a - b| / max(|b|, the plane's largest |b| over the points), the maximum over the points"
-    with open(os.path.join(OUT, "intake_observed.json"), "w") as fh:
-        json.dump(obs, fh, indent=1, sort_keys=True)
-        fh.write("\n")
+    GC.write_observed(OUT, "intake_observed.json", obs)
 
 
 if __name__ == "__main__":

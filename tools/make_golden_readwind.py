@@ -1,6 +1,6 @@
 """Generates tests/golden/readwind_0.npz and tests/golden/readwind_observed.json by RUNNING the reference's own GRIB2WGRID (src/ecwam/grib2wgrid.F90,
-with adjust.F90, incdate.F90 and wstream_strg.F90), compiled unmodified with the ROCm flang against the stand-in modules of
-tools/readwind_driver.F90, in double and in single precision (-cpp -O2 -ffp-contract=off, -DSINGLE).  The routine asks a stand-in GRIB decoder
+with adjust.F90, incdate.F90 and wstream_strg.F90) behind tools/readwind_driver.F90, built by oracle/ref_build.py::build_driver in double and in
+single precision.  The routine asks a stand-in GRIB decoder
 (a YOWGRIB that answers the keys from a table) for the message; READWIND's fill and CURRENT2WAM's three statements are bound to files and to the
 message passing library, so the driver restates those few statements around the reference's FIELD.  Everything is built in a temporary directory
 outside the tree; the reference's text is read by the compiler, never copied.  The fixture holds outputs only, per case and precision: FIELD of the
@@ -19,10 +19,8 @@ each |a - b| / max(|b|, the plane's largest |b|) over the cells that are not PMI
 
     python tools/make_golden_readwind.py <root of the reference tree> [<directory to write to; default tests/golden>]
 """
-import json
 import os
 import shutil
-import subprocess
 import sys
 import tempfile
 
@@ -32,39 +30,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import readwind_ref as F  # noqa: E402  (the construction of the inputs and the restatement, shared with the tests)
+import golden_common as GC  # noqa: E402
 
-if len(sys.argv) < 2:
-    sys.exit(__doc__)
-REF = sys.argv[1]
-OUT = sys.argv[2] if len(sys.argv) > 2 else F.GOLDEN
-FLANG = shutil.which("amdflang") or "/opt/rocm/lib/llvm/bin/flang"
-LIMIT = 600_000
-SOURCES = ("grib2wgrid.F90", "adjust.F90", "incdate.F90", "wstream_strg.F90")
-INTFB = ("abort1", "adjust", "incdate", "wstream_strg")      # external procedures with plain arguments: empty interface files do
-
-
-def build(tmp, single):
-    d = os.path.join(tmp, "sp" if single else "dp")
-    os.makedirs(d)
-    for n in INTFB:
-        open(os.path.join(d, n + ".intfb.h"), "w").close()
-    flags = ["-cpp", "-O2", "-ffp-contract=off", "-module-dir", d, "-I", d] + (["-DSINGLE"] if single else [])
-    objs = []
-    for src in [os.path.join(ROOT, "tools", "readwind_driver.F90")] + [os.path.join(REF, "src", "ecwam", n) for n in SOURCES]:
-        o = os.path.join(d, os.path.basename(src).replace(".F90", ".o"))
-        subprocess.run([FLANG, *flags, "-c", src, "-o", o], check=True)
-        objs.append(o)
-    exe = os.path.join(d, "readwind_driver")
-    subprocess.run([FLANG, "-o", exe, *objs], check=True)
-    return exe
-
-
-def _r(*a):
-    return b"".join(np.ascontiguousarray(np.asarray(x, "<f8")).tobytes() for x in a)
-
-
-def _i(*a):
-    return b"".join(np.ascontiguousarray(np.asarray(x, "<i4")).tobytes() for x in a)
+REF, OUT = GC.arguments(__doc__, F.GOLDEN)
+ROUTINES = ("grib2wgrid", "adjust", "incdate", "wstream_strg")
+_r, _i = GC.r, GC.i
 
 
 def _name(s, n=40):
@@ -90,10 +60,9 @@ def _message(keys, values):
 
 def run(exe, tmp, prec, c):
     """-> {case: {key: array}} of one precision"""
-    fin, fout = os.path.join(tmp, "in.bin"), os.path.join(tmp, "out.bin")
     T = F.dtype_of(prec)
     order = []
-    with open(fin, "wb") as fh:
+    with open(GC.infile(tmp), "wb") as fh:
         fh.write(_i(F.NX, F.NY, F.NROW, F.KLONRGG, c["ifromij"], c["jfromij"]) + _r(c["xlon"], c["ylat"], F.PMISS, F.ROAIR, F.WSTAR0, F.WLOWEST, F.CURRENT_MAX, F.SENT))
         for name in F.CASES:
             fh.write(_i(2))
@@ -104,8 +73,7 @@ def run(exe, tmp, prec, c):
             fh.write(_i(3))
             order.append((name, None))
         fh.write(_i(0))
-    subprocess.run([exe, fin, fout], check=True, stdout=subprocess.DEVNULL)
-    flat = np.fromfile(fout, "<f8")
+    flat = GC.drive(exe, tmp)
     res, at = {n: {} for n in F.CASES}, 0
 
     def take(n, kind=T):
@@ -132,7 +100,8 @@ def main():
     tmp = tempfile.mkdtemp(prefix="golden_readwind_")
     try:
         c = F.make_cases()
-        ref = {p: run(build(tmp, p == "sp"), tmp, p, c) for p in ("dp", "sp")}
+        exe = GC.executables(REF, "readwind", ROUTINES, tmp, standins=("YOWGRIB",))
+        ref = {p: run(exe[p], tmp, p, c) for p in ("dp", "sp")}
     finally:
         shutil.rmtree(tmp, ignore_errors=True)
     kinds = ("restatement_vs_reference_dp", "restatement_vs_reference_sp", "reference_sp_vs_dp")
@@ -180,17 +149,12 @@ def main():
                     arrays[f"{key}_{name}"] = a
                 else:
                     arrays[f"{key}_{name}_{p}"] = a
-    path = os.path.join(OUT, "readwind_0.npz")
-    np.savez_compressed(path, **arrays)
-    assert os.path.getsize(path) <= LIMIT, os.path.getsize(path)
-    print(path, os.path.getsize(path), "bytes")
+    GC.write_npz(OUT, "readwind_0.npz", arrays)
     obs["branches"] = sorted(taken)
     obs["smallest_direction_vector"] = cond
     obs["error_measure"] = ("per field: |a - b| / max(|b|, the field's largest |b|) over the cells that are not PMISS, the maximum; dir and fg_WDWAVE: the "
                             "difference on the circle over the period (360 degrees, 2 pi)")
-    with open(os.path.join(OUT, "readwind_observed.json"), "w") as fh:
-        json.dump(obs, fh, indent=1, sort_keys=True)
-        fh.write("\n")
+    GC.write_observed(OUT, "readwind_observed.json", obs)
 
 
 if __name__ == "__main__":

@@ -1,6 +1,6 @@
 """Generates tests/golden/restart_0.npz and tests/golden/restart_observed.json by RUNNING the reference's own CDUSTARZ0, CHNKMIN, WRITEFL, WRITESTRESS
-and READSTRESS (src/ecwam/*.F90), compiled unmodified with the ROCm flang against the stand-in modules of tools/restart_driver.F90, in double and in
-single precision (-cpp -O2 -ffp-contract=off, -DSINGLE).  BUILDSTRESS, READWGRIB, SAVSTRESS and GETSTRESS are bound to files and to the message
+and READSTRESS (src/ecwam/*.F90) behind tools/restart_driver.F90, built by oracle/ref_build.py::build_driver with the reference's own modules in
+double and in single precision.  BUILDSTRESS, READWGRIB, SAVSTRESS and GETSTRESS are bound to files and to the message
 passing library, so the driver restates their statements on the fields around the reference's routines; IWAM_GET_UNIT is a stand-in that opens the
 file in the byte order of the machine (the driver's header says why).  Everything is built in a temporary directory outside the tree; the
 reference's text is read by the compiler, never copied.  The fixture holds, per precision: the rows of ff after every case of
@@ -23,10 +23,8 @@ steps, of which the one closest to 1 is recorded, and the relative change one fu
 
     python tools/make_golden_restart.py <root of the reference tree> [<directory to write to; default tests/golden>]
 """
-import json
 import os
 import shutil
-import subprocess
 import sys
 import tempfile
 
@@ -38,60 +36,22 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import reference_cases as RC  # noqa: E402
 import restart_ref as F  # noqa: E402  (the construction of the inputs and the restatement, shared with the tests)
 from ecwam_amd import synthetic as syn  # noqa: E402
+import golden_common as GC  # noqa: E402
 
-if len(sys.argv) < 2:
-    sys.exit(__doc__)
-REF = sys.argv[1]
-OUT = sys.argv[2] if len(sys.argv) > 2 else F.GOLDEN
-FLANG = shutil.which("amdflang") or "/opt/rocm/lib/llvm/bin/flang"
-LIMIT = 600_000
-SOURCES = ("cdustarz0.F90", "chnkmin.F90", "writefl.F90", "writestress.F90", "readstress.F90")
-# the interface of the stand-in IWAM_GET_UNIT (a function: the including routines need its type); ABORT1 has plain arguments: an empty file does
-IWAM_GET_UNIT_INTFB = """INTERFACE
-FUNCTION IWAM_GET_UNIT (KUSO, CDNAME, CDACCESS, CDFORM, KRECL, CDACTION)
-USE PARKIND_WAVE, ONLY : JWIM
-INTEGER(KIND=JWIM) :: IWAM_GET_UNIT
-INTEGER(KIND=JWIM), INTENT(IN) :: KUSO
-CHARACTER(LEN=*), INTENT(IN) :: CDNAME, CDACTION
-CHARACTER(LEN=1), INTENT(IN) :: CDACCESS, CDFORM
-INTEGER(KIND=JWIM), INTENT(IN) :: KRECL
-END FUNCTION IWAM_GET_UNIT
-END INTERFACE
-"""
+REF, OUT = GC.arguments(__doc__, F.GOLDEN)
+ROUTINES = ("cdustarz0", "chnkmin", "writefl", "writestress", "readstress")
+STANDINS = ("YOWUNBLKRORD",)      # the three file routines name it only behind WAM_HAVE_UNWAM, which is not defined: no module is supplied
 FILES = ("BLS_ll1d", "BLS_relab", "LAW_ll1d", "LAW_relab")
 
 
-def build(tmp, single):
-    d = os.path.join(tmp, "sp" if single else "dp")
-    os.makedirs(d)
-    open(os.path.join(d, "abort1.intfb.h"), "w").close()
-    with open(os.path.join(d, "iwam_get_unit.intfb.h"), "w") as fh:
-        fh.write(IWAM_GET_UNIT_INTFB)
-    flags = ["-cpp", "-O2", "-ffp-contract=off", '-D__FILENAME__="reference"', "-module-dir", d, "-I", d] + (["-DSINGLE"] if single else [])
-    objs = []
-    for src in [os.path.join(ROOT, "tools", "restart_driver.F90")] + [os.path.join(REF, "src", "ecwam", n) for n in SOURCES]:
-        o = os.path.join(d, os.path.basename(src).replace(".F90", ".o"))
-        subprocess.run([FLANG, *flags, "-c", src, "-o", o], check=True)
-        objs.append(o)
-    exe = os.path.join(d, "restart_driver")
-    subprocess.run([FLANG, "-o", exe, *objs], check=True)
-    return exe
-
-
-def _r(*a):
-    return b"".join(np.ascontiguousarray(np.asarray(x, "<f8")).tobytes() for x in a)
-
-
-def _i(*a):
-    return b"".join(np.ascontiguousarray(np.asarray(x, "<i4")).tobytes() for x in a)
+_r, _i = GC.r, GC.i
 
 
 def run(exe, tmp, prec, inp, state):
     """-> the arrays of one precision, keyed as the fixture keys them without the precision"""
     d = os.path.join(tmp, prec)
-    fin, fout = os.path.join(d, "in.bin"), os.path.join(d, "out.bin")
     T = F.dtype_of(prec)
-    with open(fin, "wb") as fh:
+    with open(GC.infile(d), "wb") as fh:
         fh.write(_i(F.N, F.NANG, F.NFRE, F.NCELL, inp["map_in"] + 1, F.permutation() + 1))
         t = F.tables(prec)
         fh.write(_r([float(getattr(t, k)) for k in F.CONSTANTS], F.ZMISS, F.PRCHAR))
@@ -103,8 +63,7 @@ def run(exe, tmp, prec, inp, state):
         fh.write("".join(F.DATES).encode("ascii"))
         depth = RC.depthprpt_depths()
         fh.write(_i(depth.size) + _r(depth, float(t.GAM_B_J)))
-    subprocess.run([exe, fin, fout, d], check=True, stdout=subprocess.DEVNULL)
-    flat = np.fromfile(fout, "<f8")
+    flat = GC.drive(exe, d, d)
     res, at = {}, 0
 
     def take(n, kind=T):
@@ -161,7 +120,8 @@ def main():
     tmp = tempfile.mkdtemp(prefix="golden_restart_")
     try:
         inp, state = F.make_inputs(), F.restart_state()
-        ref = {p: run(build(tmp, p == "sp"), tmp, p, inp, state) for p in ("dp", "sp")}
+        exe = GC.executables(REF, "restart", ROUTINES, tmp, STANDINS, ('-D__FILENAME__="reference"',))
+        ref = {p: run(exe[p], tmp, p, inp, state) for p in ("dp", "sp")}
     finally:
         shutil.rmtree(tmp, ignore_errors=True)
     kinds = ("reference_sp_vs_dp", "restatement_vs_reference_dp", "restatement_vs_reference_sp")
@@ -230,15 +190,10 @@ def main():
                 arrays[key] = a
             else:
                 arrays[f"{key}_{p}"] = a
-    path = os.path.join(OUT, "restart_0.npz")
-    np.savez_compressed(path, **arrays)
-    assert os.path.getsize(path) <= LIMIT, os.path.getsize(path)
-    print(path, os.path.getsize(path), "bytes")
+    GC.write_npz(OUT, "restart_0.npz", arrays)
     obs["branches"] = {n: [bool(taken[i]), bool(left[i])] for i, n in enumerate(F.BRANCH_NAMES)}
     obs["error_measure"] = "per column or array: |a - b| / max(|b|, the column's largest |b|), the maximum"
-    with open(os.path.join(OUT, "restart_observed.json"), "w") as fh:
-        json.dump(obs, fh, indent=1, sort_keys=True)
-        fh.write("\n")
+    GC.write_observed(OUT, "restart_observed.json", obs)
 
 
 if __name__ == "__main__":

@@ -1,6 +1,6 @@
 """Generates tests/golden/start_<NANG>x<NFRE_RED>_<i>.npz and tests/golden/start_observed.json by RUNNING the reference's own MSTART, PEAK,
-SPECTRA, JONSWAP, SPR, UNSETICE, SDEPTHLIM and SEMEAN (src/ecwam/*.F90, with its yowjons.F90), compiled unmodified with the ROCm flang
-against the stub modules of tools/start_driver.F90 and empty *.intfb.h files, in double and in single precision (-ffp-contract=off).
+SPECTRA, JONSWAP, SPR, UNSETICE, SDEPTHLIM and SEMEAN (src/ecwam/*.F90) behind tools/start_driver.F90, built by
+oracle/ref_build.py::build_driver with the reference's own modules in double and in single precision.
 Everything is built in a temporary directory outside the tree; the reference's text is read by the compiler, never copied.  The fixtures
 hold data only: the two frequency tables and what the routines returned on the active rows, per call (tests/start_ref.py::calls); the
 inputs are those of tests/start_ref.py::make_cases, which the tests rebuild (float32-representable, so that both precisions see the same
@@ -20,14 +20,12 @@ each per bin over the point's largest bin.  A result is split over files so that
 inputs of MSTART and UNSETICE with the full shape (neither routine knows NFRE_RED): the tool runs them, requires the same results and records
 the tail only.
 
-    python tools/make_golden_start.py <root of the reference tree>
+    python tools/make_golden_start.py <root of the reference tree> [<directory to write to; default tests/golden>]
 """
 import glob
 import io
-import json
 import os
 import shutil
-import subprocess
 import sys
 import tempfile
 
@@ -37,30 +35,12 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import start_ref as S  # noqa: E402  (the construction of the inputs and the restatement, shared with the tests)
+import golden_common as GC  # noqa: E402
 
-if len(sys.argv) < 2:
-    sys.exit(__doc__)
-REF = sys.argv[1]
-FLANG = shutil.which("amdflang") or "/opt/rocm/lib/llvm/bin/flang"
-LIMIT = 600_000
-SOURCES = ("yowjons.F90", "semean.F90", "sdepthlim.F90", "jonswap.F90", "spr.F90", "peak.F90", "spectra.F90", "mstart.F90", "unsetice.F90")
+REF, OUT = GC.arguments(__doc__, S.GOLDEN)
+LIMIT = GC.LIMIT
+ROUTINES = ("semean", "sdepthlim", "jonswap", "spr", "peak", "spectra", "mstart", "unsetice")
 A = slice(S.KIJS, S.KIJL)
-
-
-def build(tmp, single):
-    d = os.path.join(tmp, "sp" if single else "dp")
-    os.makedirs(d)
-    for h in ("peak", "spectra", "jonswap", "spr", "sdepthlim", "semean"):
-        open(os.path.join(d, h + ".intfb.h"), "w").close()
-    flags = ["-cpp", "-O2", "-ffp-contract=off", "-module-dir", d, "-I", d] + (["-DSINGLE"] if single else [])
-    objs = []
-    for src in [os.path.join(ROOT, "tools", "start_driver.F90")] + [os.path.join(REF, "src", "ecwam", n) for n in SOURCES]:
-        o = os.path.join(d, os.path.basename(src).replace(".F90", ".o"))
-        subprocess.run([FLANG, *flags, "-c", src, "-o", o], check=True)
-        objs.append(o)
-    exe = os.path.join(d, "start_driver")
-    subprocess.run([FLANG, "-o", exe, *objs], check=True)
-    return exe
 
 
 def _f(a):      # [ij][K][M] -> the bytes of FL1(IJ,K,M)
@@ -71,9 +51,8 @@ def run(exe, tmp, shape, prec, cases):
     nang, nfre, nfre_red = shape
     T = np.float32 if prec == "sp" else np.float64
     n = S.KIJL - S.KIJS
-    fin, fout = os.path.join(tmp, "in.bin"), os.path.join(tmp, "out.bin")
     names = S.calls(shape)
-    with open(fin, "wb") as fh:
+    with open(GC.infile(tmp), "wb") as fh:
         t = S.tables(shape, T)
         fh.write(np.array([n, nang, nfre], "<i4").tobytes())
         for a in (t.FR, t.TH, t.DFIM, t.FR5):
@@ -99,8 +78,7 @@ def run(exe, tmp, shape, prec, cases):
                 fh.write(np.asarray(ff[:, S.C_EMAXDPT], "<f8").tobytes())
                 fh.write(_f(c["fl"][A]))
         fh.write(np.array([0], "<i4").tobytes())
-    subprocess.run([exe, fin, fout], check=True)
-    a = np.fromfile(fout, "<f8").reshape(len(names), nfre, nang, n).transpose(0, 3, 2, 1)
+    a = GC.drive(exe, tmp).reshape(len(names), nfre, nang, n).transpose(0, 3, 2, 1)
     return {name: np.ascontiguousarray(a[i]) for i, name in enumerate(names)}
 
 
@@ -132,7 +110,7 @@ def same_branches(shape, cases, ref):
 
 def write_split(tag, arrays):
     """The arrays into start_<tag>_<i>.npz, a new file whenever the one at hand would pass LIMIT."""
-    for old in glob.glob(os.path.join(S.GOLDEN, f"start_{tag}_*.npz")):
+    for old in glob.glob(os.path.join(OUT, f"start_{tag}_*.npz")):
         os.remove(old)
     files, cur = [], {}
 
@@ -151,7 +129,7 @@ def write_split(tag, arrays):
     files.append(cur)
     total = 0
     for i, d in enumerate(files):
-        path = os.path.join(S.GOLDEN, f"start_{tag}_{i}.npz")
+        path = os.path.join(OUT, f"start_{tag}_{i}.npz")
         np.savez_compressed(path, **d)
         total += os.path.getsize(path)
         print(path, os.path.getsize(path), "bytes", sorted(d))
@@ -165,7 +143,7 @@ def main():
     total = 0
     recorded = {}
     try:
-        exe = {p: build(tmp, p == "sp") for p in ("dp", "sp")}
+        exe = GC.executables(REF, "start", ROUTINES, tmp)
         for shape in S.SHAPES:
             cases = S.make_cases(shape)
             ref = {p: run(exe[p], tmp, shape, p, cases) for p in ("dp", "sp")}
@@ -193,9 +171,7 @@ def main():
         shutil.rmtree(tmp, ignore_errors=True)
     obs["per_call"] = per_call
     obs["error_measure"] = "per point, the largest |a - b| over the point's largest |b| bin; the maximum over the points"
-    with open(os.path.join(S.GOLDEN, "start_observed.json"), "w") as fh:
-        json.dump(obs, fh, indent=1, sort_keys=True)
-        fh.write("\n")
+    GC.write_observed(OUT, "start_observed.json", obs)
     print("fixtures:", total, "bytes")
 
 

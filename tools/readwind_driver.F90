@@ -1,9 +1,10 @@
-! Driver of tools/make_golden_readwind.py: calls the reference's GRIB2WGRID, compiled unmodified from the reference tree (with its ADJUST, INCDATE and
-! WSTREAM_STRG), on the records of a stream file and writes what it returns.  The modules below are the stand-ins the routine needs: the kinds of
-! PARKIND_WAVE (-DSINGLE: the single precision build), YOMHOOK, and a YOWGRIB whose generic IGRIB_GET_VALUE / IGRIB_SET_VALUE answer integer, real,
-! character, integer-array and real-array keys from a table this program fills from the file -- a stand-in for the GRIB decoder, not a decoder.  KRET
-! is the optional fourth argument, which is also how the routine's positional IERR arrives: a key the table does not hold gives KRET = 1 where KRET is
-! present and stops the program where it is not.  abort1.intfb.h is an empty file of the build directory; ABORT1 and GSTATS are the stubs at the end.
+! Driver of tools/make_golden_readwind.py: calls the reference's GRIB2WGRID (with its ADJUST, INCDATE and WSTREAM_STRG) on the records of a stream
+! file and writes what it returns.  It is built by oracle/ref_build.py::build_driver: the routines and PARKIND_WAVE are the reference's own files,
+! compiled unmodified in both precisions, behind the stand-ins of oracle/ref_stubs.F90 for what other packages supply.  One module is the driver's
+! own, and the point of it: a YOWGRIB whose generic IGRIB_GET_VALUE / IGRIB_SET_VALUE answer integer, real, character, integer-array and
+! real-array keys from a table this program fills from the file -- a stand-in for the GRIB decoder, not a decoder.  KRET is the optional fourth
+! argument, which is also how the routine's positional IERR arrives: a key the table does not hold gives KRET = 1 where KRET is present and stops
+! the program where it is not.
 ! READWIND and CURRENT2WAM are bound to files and to the message passing library, so their few statements on the field (readwind.F90:341-494,
 ! current2wam.F90:247-279) are restated here around the reference's FIELD.
 ! Input  (stream, little endian): NX, NY, NPTS (int32); KLONRGG(NY) (int32, south to north); IFROMIJ(NPTS), JFROMIJ(NPTS) (int32, 1-based); XLON(NX,NY),
@@ -16,30 +17,6 @@
 !          2 reset FIELDG(NX,NY,13) to SENTINEL, UCUR and VCUR(NPTS) to SENTINEL
 !          3 -> FIELDG(NX,NY,13), UCUR(NPTS), VCUR(NPTS)
 ! Output (stream): per record the arrays listed, real64 (integers and working-precision results widened).
-MODULE PARKIND_WAVE
-  IMPLICIT NONE
-  INTEGER, PARAMETER :: JWIM = SELECTED_INT_KIND(9)
-#ifdef SINGLE
-  INTEGER, PARAMETER :: JWRB = SELECTED_REAL_KIND(6, 37)
-#else
-  INTEGER, PARAMETER :: JWRB = SELECTED_REAL_KIND(13, 300)
-#endif
-  INTEGER, PARAMETER :: JWRU = SELECTED_REAL_KIND(13, 300)
-  INTEGER, PARAMETER :: JWRO = SELECTED_REAL_KIND(13, 300)
-END MODULE PARKIND_WAVE
-
-MODULE YOMHOOK
-  IMPLICIT NONE
-  INTEGER, PARAMETER :: JPHOOK = SELECTED_REAL_KIND(13, 300)
-  LOGICAL :: LHOOK = .FALSE.
-CONTAINS
-  SUBROUTINE DR_HOOK(CDNAME, KSWITCH, PKEY)
-    CHARACTER(LEN=*), INTENT(IN) :: CDNAME
-    INTEGER, INTENT(IN) :: KSWITCH
-    REAL(KIND=JPHOOK), INTENT(INOUT) :: PKEY
-  END SUBROUTINE DR_HOOK
-END MODULE YOMHOOK
-
 MODULE YOWGRIB
   USE PARKIND_WAVE, ONLY : JWIM, JWRB
   IMPLICIT NONE
@@ -170,24 +147,7 @@ PROGRAM READWIND_DRIVER
   USE PARKIND_WAVE, ONLY : JWIM, JWRB
   USE YOWGRIB
   IMPLICIT NONE
-  INTERFACE
-    SUBROUTINE GRIB2WGRID (IU06, KPROMA, KGRIB_HANDLE, KGRIB, ISIZE, LLUNSTR, LLCHKINT, NGY, KRGG, KLONRGG_LOC, NXS, NXE, NYS, NYE, XLON, YLAT, &
- &                         PMISS, PPREC, PPEPS, CDATE, IFORP, IPARAM, KZLEV, KKK, MMM, FIELD)
-      USE PARKIND_WAVE, ONLY : JWIM, JWRB
-      INTEGER(KIND=JWIM), INTENT(IN) :: IU06, KPROMA, KGRIB_HANDLE, ISIZE
-      INTEGER(KIND=JWIM), INTENT(IN) :: NGY, KRGG
-      INTEGER(KIND=JWIM), INTENT(IN) :: NXS, NXE, NYS, NYE
-      INTEGER(KIND=JWIM), INTENT(IN) :: KGRIB(ISIZE)
-      INTEGER(KIND=JWIM), INTENT(IN) :: KLONRGG_LOC(NGY)
-      INTEGER(KIND=JWIM), INTENT(OUT) :: IFORP, IPARAM, KZLEV, KKK, MMM
-      REAL(KIND=JWRB), INTENT(IN) :: PMISS, PPREC, PPEPS
-      REAL(KIND=JWRB), DIMENSION(NXS:NXE, NYS:NYE), INTENT(IN) :: XLON, YLAT
-      REAL(KIND=JWRB), DIMENSION(NXS:NXE, NYS:NYE), INTENT(OUT) :: FIELD
-      CHARACTER(LEN=14), INTENT(OUT) :: CDATE
-      LOGICAL, INTENT(IN) :: LLUNSTR
-      LOGICAL, INTENT(IN) :: LLCHKINT
-    END SUBROUTINE GRIB2WGRID
-  END INTERFACE
+#include "grib2wgrid.intfb.h"
   INTEGER, PARAMETER :: NFG = 13
   ! the planes of FIELDG in the order of ecwam_hip_forcing.h
   INTEGER, PARAMETER :: JUWND = 1, JVWND = 2, JAIRD = 3, JWSTAR = 4, JCICOVER = 5, JCITHICK = 6, JWSWAVE = 9, JWDWAVE = 10
@@ -342,12 +302,3 @@ PROGRAM READWIND_DRIVER
   CLOSE(10)
   CLOSE(11)
 END PROGRAM READWIND_DRIVER
-
-SUBROUTINE ABORT1
-  WRITE(0,*) 'readwind_driver: the reference called ABORT1'
-  ERROR STOP 7
-END SUBROUTINE ABORT1
-
-SUBROUTINE GSTATS(KNUM, KSWITCH)
-  INTEGER :: KNUM, KSWITCH
-END SUBROUTINE GSTATS

@@ -1,6 +1,7 @@
-! Driver of tools/make_golden_restart.py: calls the reference's CDUSTARZ0, CHNKMIN, WRITEFL, WRITESTRESS and READSTRESS, compiled unmodified from the
-! reference tree, behind the stand-in modules below (the kinds of PARKIND_WAVE, -DSINGLE: the single precision build; the constants of YOWPCONS,
-! YOWPHYS and YOWWIND, whose run-time values this program reads from its input; YOWMPP, YOWPARAM, YOWSTAT, YOWSPEC, YOWTEST, YOWABORT, YOMHOOK).
+! Driver of tools/make_golden_restart.py: calls the reference's CDUSTARZ0, CHNKMIN, WRITEFL, WRITESTRESS and READSTRESS.  It is built by
+! oracle/ref_build.py::build_driver: the routines and the modules they use are the reference's own files, compiled unmodified in both precisions,
+! behind the stand-ins of oracle/ref_stubs.F90 for what other packages supply.  The program fills the run-time values of YOWPCONS, YOWPHYS and
+! YOWWIND from its input and compares what the reference declares a PARAMETER; it holds no module of its own.
 ! BUILDSTRESS, READWGRIB, SAVSTRESS and GETSTRESS are bound to files and to the message passing library, so their statements on the fields
 ! (buildstress.F90:236-242, 279-313; readwgrib.F90:165-175; savstress.F90:112-127; getstress.F90:95-97, 150-165, 294-303) are restated here around
 ! the reference's routines.  IWAM_GET_UNIT is a stand-in that opens the file as the reference's does, but in the byte order of the machine: the
@@ -12,92 +13,6 @@
 !        CHARACTER(14); ND (int32), DEPTH(ND), GAM_B_J (real64).  The third argument is the directory the four files BLS_ll1d, BLS_relab, LAW_ll1d, LAW_relab are written to.
 ! Output (stream): per case FF(16,N), CD(N), the branch code (N), real64; then what READSTRESS returned from LAW_ll1d and from LAW_relab, RFIELD(N,16)
 !        each, real64; EMAXDPT(ND), real64.
-MODULE PARKIND_WAVE
-  IMPLICIT NONE
-  INTEGER, PARAMETER :: JWIM = SELECTED_INT_KIND(9)
-#ifdef SINGLE
-  INTEGER, PARAMETER :: JWRB = SELECTED_REAL_KIND(6, 37)
-#else
-  INTEGER, PARAMETER :: JWRB = SELECTED_REAL_KIND(13, 300)
-#endif
-  INTEGER, PARAMETER :: JWRU = SELECTED_REAL_KIND(13, 300)
-  INTEGER, PARAMETER :: JWRO = SELECTED_REAL_KIND(13, 300)
-END MODULE PARKIND_WAVE
-
-MODULE YOMHOOK
-  IMPLICIT NONE
-  INTEGER, PARAMETER :: JPHOOK = SELECTED_REAL_KIND(13, 300)
-  LOGICAL :: LHOOK = .FALSE.
-CONTAINS
-  SUBROUTINE DR_HOOK(CDNAME, KSWITCH, PKEY)
-    CHARACTER(LEN=*), INTENT(IN) :: CDNAME
-    INTEGER, INTENT(IN) :: KSWITCH
-    REAL(KIND=JPHOOK), INTENT(INOUT) :: PKEY
-  END SUBROUTINE DR_HOOK
-END MODULE YOMHOOK
-
-MODULE YOWPCONS
-  USE PARKIND_WAVE, ONLY : JWRB
-  IMPLICIT NONE
-  REAL(KIND=JWRB), PARAMETER :: C1CD = 1.03E-3_JWRB
-  REAL(KIND=JWRB), PARAMETER :: C2CD = 0.04E-3_JWRB
-  REAL(KIND=JWRB), PARAMETER :: P1CD = 1.48_JWRB
-  REAL(KIND=JWRB), PARAMETER :: P2CD = -0.21_JWRB
-  REAL(KIND=JWRB) :: CDMAX, EPSUS, EPSU10, G
-END MODULE YOWPCONS
-
-MODULE YOWPHYS
-  USE PARKIND_WAVE, ONLY : JWRB
-  IMPLICIT NONE
-  REAL(KIND=JWRB) :: XKAPPA, RNUM, ALPHA, ALPHAMIN, CHNKMIN_U
-END MODULE YOWPHYS
-
-MODULE YOWWIND
-  USE PARKIND_WAVE, ONLY : JWRB
-  IMPLICIT NONE
-  REAL(KIND=JWRB) :: WSPMIN
-  CHARACTER(LEN=14) :: CDAWIFL, CDATEWO, CDATEFL
-END MODULE YOWWIND
-
-MODULE YOWSTAT
-  IMPLICIT NONE
-  CHARACTER(LEN=14) :: CDTPRO
-END MODULE YOWSTAT
-
-MODULE YOWMPP
-  USE PARKIND_WAVE, ONLY : JWIM
-  IMPLICIT NONE
-  INTEGER(KIND=JWIM) :: NPROC = 1
-END MODULE YOWMPP
-
-MODULE YOWPARAM
-  IMPLICIT NONE
-  LOGICAL :: LL1D = .TRUE., LLUNSTR = .FALSE.
-END MODULE YOWPARAM
-
-MODULE YOWSPEC
-  USE PARKIND_WAVE, ONLY : JWIM
-  IMPLICIT NONE
-  INTEGER(KIND=JWIM), ALLOCATABLE :: IJ2NEWIJ(:)
-END MODULE YOWSPEC
-
-MODULE YOWTEST
-  USE PARKIND_WAVE, ONLY : JWIM
-  IMPLICIT NONE
-  INTEGER(KIND=JWIM) :: IU06 = -1      ! IWAM_GET_UNIT prints nothing
-END MODULE YOWTEST
-
-MODULE YOWABORT
-  IMPLICIT NONE
-CONTAINS
-  SUBROUTINE WAM_ABORT(CDMSG, CDFILE, KLINE)
-    CHARACTER(LEN=*), INTENT(IN), OPTIONAL :: CDMSG, CDFILE
-    INTEGER, INTENT(IN), OPTIONAL :: KLINE
-    IF (PRESENT(CDMSG)) WRITE(0,*) 'restart_driver: the reference called WAM_ABORT: ', CDMSG
-    ERROR STOP 8
-  END SUBROUTINE WAM_ABORT
-END MODULE YOWABORT
-
 PROGRAM RESTART_DRIVER
   USE PARKIND_WAVE, ONLY : JWIM, JWRB
   USE YOWPCONS, ONLY : CDMAX, EPSUS, EPSU10, G
@@ -105,16 +20,10 @@ PROGRAM RESTART_DRIVER
   USE YOWWIND, ONLY : WSPMIN, CDAWIFL, CDATEWO, CDATEFL
   USE YOWSTAT, ONLY : CDTPRO
   USE YOWMPP, ONLY : NPROC
-  USE YOWPARAM, ONLY : LL1D
+  USE YOWPARAM, ONLY : LL1D, LLUNSTR
   USE YOWSPEC, ONLY : IJ2NEWIJ
   IMPLICIT NONE
-  INTERFACE
-    FUNCTION CHNKMIN(U10)
-      USE PARKIND_WAVE, ONLY : JWRB
-      REAL(KIND=JWRB) :: CHNKMIN
-      REAL(KIND=JWRB), INTENT(IN) :: U10
-    END FUNCTION CHNKMIN
-  END INTERFACE
+#include "chnkmin.intfb.h"
   INTEGER, PARAMETER :: NREAL = 16
   INTEGER, PARAMETER :: BR_UWAVE = 1, BR_CD = 2, BR_WSPMIN = 4, BR_Z0MIN = 8, BR_EPSUS = 16, BR_FLOOR_Z0M = 32, BR_TAUW0 = 64
   CHARACTER(LEN=512) :: FIN, FOUT, DIR
@@ -146,10 +55,10 @@ PROGRAM RESTART_DRIVER
   READ(10) MAPIN, PERM
   READ(10) R8
   WSPMIN = REAL(R8(1), JWRB)
-  CDMAX = REAL(R8(2), JWRB)
-  EPSUS = REAL(R8(3), JWRB)
-  EPSU10 = REAL(R8(4), JWRB)
-  XKAPPA = REAL(R8(5), JWRB)
+  IF (REAL(R8(2), JWRB) /= CDMAX) ERROR STOP 'CDMAX'
+  IF (REAL(R8(3), JWRB) /= EPSUS) ERROR STOP 'EPSUS'
+  IF (REAL(R8(4), JWRB) /= EPSU10) ERROR STOP 'EPSU10'
+  IF (REAL(R8(5), JWRB) /= XKAPPA) ERROR STOP 'XKAPPA'
   RNUM = REAL(R8(6), JWRB)
   ALPHA = REAL(R8(7), JWRB)
   ALPHAMIN = REAL(R8(8), JWRB)
@@ -158,6 +67,7 @@ PROGRAM RESTART_DRIVER
   G = REAL(R8(11), JWRB)
   ZMISS = REAL(R8(12), JWRB)
   PRCHAR = REAL(R8(13), JWRB)
+  LLUNSTR = .FALSE.
   READ(10) FF8
   FF0 = REAL(FF8, JWRB)
   READ(10) P8
@@ -346,8 +256,3 @@ FUNCTION IWAM_GET_UNIT (KUSO, CDNAME, CDACCESS, CDFORM, KRECL, CDACTION)
   ENDIF
   IWAM_GET_UNIT = JUME
 END FUNCTION IWAM_GET_UNIT
-
-SUBROUTINE ABORT1
-  WRITE(0,*) 'restart_driver: the reference called ABORT1'
-  ERROR STOP 7
-END SUBROUTINE ABORT1

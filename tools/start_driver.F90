@@ -1,9 +1,10 @@
-! Driver of tools/make_golden_start.py: calls the reference's MSTART (with PEAK, SPECTRA, JONSWAP, SPR), UNSETICE and SDEPTHLIM (with SEMEAN),
-! compiled unmodified from the reference tree together with its YOWJONS, on the records of a stream file and writes what they return.  The
-! modules below are the stub those routines need: the kinds of PARKIND_WAVE (-DSINGLE: the single precision build) and the members of the
-! model's modules that the routines name, as variables this program fills from the file (so that the reference sees the tables of
-! ecwam_amd/tables.py, the ones the device holds).  For the tail of GETSPEC the program restates the fill loop of getspec.F90:650-656 -- three
-! lines inside a routine that reads GRIB files -- and calls the reference's SDEPTHLIM, as getspec.F90:658 does.
+! Driver of tools/make_golden_start.py: calls the reference's MSTART (with PEAK, SPECTRA, JONSWAP, SPR), UNSETICE and SDEPTHLIM (with SEMEAN) on
+! the records of a stream file and writes what they return.  It is built by oracle/ref_build.py::build_driver: the routines and the modules
+! they use are the reference's own files, compiled unmodified in both precisions, behind the stand-ins of oracle/ref_stubs.F90 for what other
+! packages supply; the driver holds no module of its own.  The program fills the modules' variables from the file, so that the reference sees
+! the tables of ecwam_amd/tables.py, the ones the device holds, and compares what the reference declares a PARAMETER (EPSMIN, WETAIL, FLMIN).
+! For the tail of GETSPEC the program restates the fill loop of getspec.F90:650-656 -- three lines inside a routine that reads GRIB files --
+! and calls the reference's SDEPTHLIM, as getspec.F90:658 does.
 ! Input  (stream, little endian): NPTS, NANG, NFRE (int32); FR(NFRE), TH(NANG), DFIM(NFRE), FR5(NFRE), then G, PI, ZPI, ZPI4GM2, EPSMIN, DELTH,
 !        WETAIL, FLMIN (real64); then records, each led by an int32:
 !          1 MSTART:   IOPTI (int32); FETCH, FRMAX, THETAQ, FM, ALFA, ZGAMMA, SA, SB (real64); WSWAVE(NPTS), WDWAVE(NPTS)
@@ -13,92 +14,6 @@
 !          0 the end
 !        Every real is representable in the working precision.
 ! Output (stream): per record FL1(NPTS,NANG,NFRE) (real64): the working-precision result, widened.
-MODULE PARKIND_WAVE
-  IMPLICIT NONE
-  INTEGER, PARAMETER :: JWIM = SELECTED_INT_KIND(9)
-#ifdef SINGLE
-  INTEGER, PARAMETER :: JWRB = SELECTED_REAL_KIND(6, 37)
-#else
-  INTEGER, PARAMETER :: JWRB = SELECTED_REAL_KIND(13, 300)
-#endif
-  INTEGER, PARAMETER :: JWRU = SELECTED_REAL_KIND(13, 300)
-END MODULE PARKIND_WAVE
-
-MODULE YOWPARAM
-  USE PARKIND_WAVE, ONLY : JWIM
-  IMPLICIT NONE
-  INTEGER(KIND=JWIM) :: NANG, NFRE
-END MODULE YOWPARAM
-
-MODULE YOWPCONS
-  USE PARKIND_WAVE, ONLY : JWRB
-  IMPLICIT NONE
-  REAL(KIND=JWRB) :: G, PI, ZPI, ZPI4GM2, EPSMIN, DEG, R
-END MODULE YOWPCONS
-
-MODULE YOWFRED
-  USE PARKIND_WAVE, ONLY : JWRB
-  IMPLICIT NONE
-  REAL(KIND=JWRB), ALLOCATABLE :: FR(:), TH(:), DFIM(:), FR5(:), FRM5(:)
-  REAL(KIND=JWRB) :: DELTH, WETAIL
-END MODULE YOWFRED
-
-MODULE YOWSTAT
-  IMPLICIT NONE
-  CHARACTER(LEN=14) :: CDTPRO
-  LOGICAL :: LBIWBK
-END MODULE YOWSTAT
-
-MODULE YOWWIND
-  IMPLICIT NONE
-  CHARACTER(LEN=14) :: CDAWIFL, CDATEWO, CDATEFL
-END MODULE YOWWIND
-
-MODULE YOWGRID
-  USE PARKIND_WAVE, ONLY : JWRB
-  IMPLICIT NONE
-  REAL(KIND=JWRB) :: DELPHI
-END MODULE YOWGRID
-
-MODULE YOWICE
-  USE PARKIND_WAVE, ONLY : JWRB
-  IMPLICIT NONE
-  REAL(KIND=JWRB) :: FLMIN, CITHRSH
-  LOGICAL :: LICERUN, LMASKICE
-END MODULE YOWICE
-
-MODULE YOWMAP
-  IMPLICIT NONE
-  CHARACTER(LEN=1) :: CLDOMAIN = 'g'
-END MODULE YOWMAP
-
-MODULE YOWTEXT
-  IMPLICIT NONE
-  LOGICAL :: LRESTARTED = .FALSE.
-END MODULE YOWTEXT
-
-MODULE YOWDRVTYPE
-  IMPLICIT NONE
-  TYPE ENVIRONMENT
-    INTEGER :: UNUSED
-  END TYPE ENVIRONMENT
-  TYPE FORCING_FIELDS
-    INTEGER :: UNUSED
-  END TYPE FORCING_FIELDS
-END MODULE YOWDRVTYPE
-
-MODULE YOMHOOK
-  IMPLICIT NONE
-  INTEGER, PARAMETER :: JPHOOK = SELECTED_REAL_KIND(13, 300)
-  LOGICAL :: LHOOK = .FALSE.
-CONTAINS
-  SUBROUTINE DR_HOOK(CDNAME, KSWITCH, PKEY)
-    CHARACTER(LEN=*), INTENT(IN) :: CDNAME
-    INTEGER, INTENT(IN) :: KSWITCH
-    REAL(KIND=JPHOOK), INTENT(INOUT) :: PKEY
-  END SUBROUTINE DR_HOOK
-END MODULE YOMHOOK
-
 PROGRAM START_DRIVER
   USE PARKIND_WAVE, ONLY : JWIM, JWRB
   USE YOWPARAM, ONLY : NANG, NFRE
@@ -107,6 +22,8 @@ PROGRAM START_DRIVER
   USE YOWSTAT, ONLY : LBIWBK
   USE YOWGRID, ONLY : DELPHI
   USE YOWICE, ONLY : FLMIN, CITHRSH, LICERUN, LMASKICE
+  USE YOWMAP, ONLY : CLDOMAIN
+  USE YOWTEXT, ONLY : LRESTARTED
   IMPLICIT NONE
   INTEGER, PARAMETER :: R8 = SELECTED_REAL_KIND(13, 300)
   INTEGER(KIND=JWIM) :: NPTS, OP, IOPTI, L1, L2, L3, NFRE_RED, M
@@ -140,12 +57,14 @@ PROGRAM START_DRIVER
   PI = REAL(S(2), JWRB)
   ZPI = REAL(S(3), JWRB)
   ZPI4GM2 = REAL(S(4), JWRB)
-  EPSMIN = REAL(S(5), JWRB)
+  IF (REAL(S(5), JWRB) /= EPSMIN) ERROR STOP 'EPSMIN'
   DELTH = REAL(S(6), JWRB)
-  WETAIL = REAL(S(7), JWRB)
-  FLMIN = REAL(S(8), JWRB)
+  IF (REAL(S(7), JWRB) /= WETAIL) ERROR STOP 'WETAIL'
+  IF (REAL(S(8), JWRB) /= FLMIN) ERROR STOP 'FLMIN'
   DEG = 180.0_JWRB/PI
   R = 0.0_JWRB
+  CLDOMAIN = 'g'
+  LRESTARTED = .FALSE.
   DO
     READ(11) OP
     IF (OP == 0) EXIT
