@@ -289,6 +289,47 @@ class HipContext:
             float(delpro), *self._geom(g, n, ngy), *ext, self._real(g["cosphm1_ext"], (nrow,), "COSPHM1_EXT"),
             self._real(refr, (n, 2 * self.NANG + 5), "REFR"), int(frange), kijs, kijl, nd3s, nd3e, int(copy_rest), _stream_ptr()))
 
+    # -- IPROPAGS = 0: PROPDOT with GRADI, then PROPAGS with CHECKCFL (propag_wam.F90:341-362; include/ecwam_hip_propags.h)
+    def propags_dot(self, grid_dev: dict, depth_ext, u_ext, v_ext, dot, icase: int = 1):
+        """dot [n][3 NANG + 4] = THDD(K), THDC(K), S0(K), OMDD, padding: the reference's GRADI + PROPDOT statement by statement."""
+        g = grid_dev
+        n, nland, ngy = g["n"], g["nland"], g["ngy"]
+        nrow = depth_ext.shape[0]
+        if nland >= nrow:
+            raise ValueError("PROPDOT: the *_EXT arrays must include the land row")
+        self._chk(self.lib.ecwam_hip_propags_dot(
+            self._h, n, nland, int(icase), self._int(g["kxlt"], (n,), "KXLT"), self._real(g["zdello"], (ngy,), "ZDELLO"), float(g["xdella"]),
+            self._real(g["cosph"], (ngy,), "COSPH"), self._int(g["klon"], (n, 2), "KLON"), self._int(g["klat"], (n, 2, 2), "KLAT"),
+            self._real(g["wlat"], (n, 2), "WLAT"), self._real(g["cosphm1_ext"], (nrow,), "COSPHM1_EXT"),
+            self._real(depth_ext, (nrow,), "DEPTH_EXT"), self._real(u_ext, (nrow,), "U_EXT"), self._real(v_ext, (nrow,), "V_EXT"),
+            self._real(dot, (n, _lib.propags_dot_width(self.NANG)), "DOT"), _stream_ptr()))
+
+    def propags(self, f1, f3, grid_dev: dict, cgroup_ext, delpro: float, kijs, kijl, omosnh2kd_ext=None, wavnum_ext=None, u_ext=None, v_ext=None, dot=None,
+                copy_rest=True, cfl=None, cflfail=None, icase: int = 1, irgg: int = 1, delphi: float | None = None):
+        """PROPAGS for rows [kijs, kijl).  grid_dev holds, beside the tables of grid_to_device, "dellam1_ext" (propags_grid adds it).  f3 = None: the
+        check of CHECKCFL alone.  delphi: DELPHI in the working precision; default XDELLA CIRC / 360 formed in it."""
+        g = grid_dev
+        n, nland, ngy = g["n"], g["nland"], g["ngy"]
+        nrow = f1.shape[0]
+        if nland >= nrow or cgroup_ext.shape[0] != nrow:
+            raise ValueError("PROPAGS: F1 / CGROUP_EXT without the land row")
+        npdt = np.float32 if self.dtype == torch.float32 else np.float64
+        if delphi is None:
+            delphi = float(npdt(g["xdella"]) * npdt(self.t.CIRC) / npdt(360.0))
+
+        def opt(t, shape, name):
+            return None if t is None else self._real(t, shape, name)
+
+        flags = (_lib.PROPAGS_CARTESIAN if icase == 2 else 0) | (_lib.PROPAGS_IRREGULAR if irgg == 1 else 0)
+        self._chk(self.lib.ecwam_hip_propags(
+            self._h, self._real(f1, (nrow, self.NANG, self.NFRE), "F1"), opt(f3, (nrow, self.NANG, self.NFRE), "F3"), n, nland, ngy, float(delpro), float(delphi),
+            flags, self._int(g["kxlt"], (n,), "KXLT"), self._real(g["cosph"], (ngy,), "COSPH"), self._real(g["sinph"], (ngy,), "SINPH"),
+            self._real(g["dellam1_ext"], (nrow,), "DELLAM1_EXT"), self._real(g["cosphm1_ext"], (nrow,), "COSPHM1_EXT"), self._int(g["klon"], (n, 2), "KLON"),
+            self._int(g["klat"], (n, 2, 2), "KLAT"), self._real(g["wlat"], (n, 2), "WLAT"), self._real(cgroup_ext, (nrow, self.NFRE), "CGROUP_EXT"),
+            opt(omosnh2kd_ext, (nrow, self.NFRE), "OMOSNH2KD_EXT"), opt(wavnum_ext, (nrow, self.NFRE), "WAVNUM_EXT"), opt(u_ext, (nrow,), "U_EXT"),
+            opt(v_ext, (nrow,), "V_EXT"), opt(dot, (n, _lib.propags_dot_width(self.NANG)), "DOT"), kijs, kijl, int(bool(copy_rest)),
+            opt(cfl, (n, self.NANG, _lib.PROPAGS_NCFL), "CFL"), None if cflfail is None else self._int(cflfail, (n,), "CFLFAIL"), _stream_ptr()))
+
     # -- IMPLSCH (implsch.F90:10-23)
     def implsch(self, kijs, kijl, fl1, wvprpt, ff, intf, mij, xllws, dbg=None, wam2nemo=None):
         nrow = fl1.shape[0]
@@ -1198,6 +1239,17 @@ class HipContext:
 
     def halo_unpack_host(self, fl, host_recv) -> None:
         self._chk(self.lib.ecwam_hip_halo_unpack_host(self._h, fl.data_ptr(), self._rows(fl), host_recv.data_ptr(), _stream_ptr()))
+
+
+def propags_grid(grid_dev: dict, grid, circ) -> dict:
+    """grid_dev with "dellam1_ext" added: 1 / DELLAM(KXLT) per row and 0 in the land slot, DELLAM = ZDELLO CIRC / 360 formed in the working precision
+    (readmdlconf.F90:145, mpdecomp.F90:1428), what HipContext.propags reads beside the tables of grid_to_device.  Whole-grid tables only."""
+    ref = grid_dev["cosphm1_ext"]
+    T = np.float32 if ref.dtype == torch.float32 else np.float64
+    dellam = np.asarray(grid.zdello, T) * T(circ) / T(360.0)
+    d = np.zeros(ref.shape[0], T)
+    d[:grid.nsea] = T(1) / dellam[grid.kxlt]
+    return dict(grid_dev, dellam1_ext=torch.from_numpy(d).to(ref.device))
 
 
 def grid_to_device(grid, dtype, device, lo: int = 0, hi: int | None = None, local=None) -> dict:

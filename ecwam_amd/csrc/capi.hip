@@ -764,6 +764,56 @@ int ecwam_hip_propags2_refra(ecwam_hip_ctx* c, const void* f1, void* f3, int n, 
                              copy_rest ? 1 : 0, (hipStream_t)stream);
 }
 
+// ---- IPROPAGS = 0: the first-order scheme (include/ecwam_hip_propags.h; csrc/propags.hip) ----------------------------------------------------------
+int ecwam_hip_propags_dot(ecwam_hip_ctx* c, int n, int nland, int icase, const int* kxlt, const void* zdello, double xdella, const void* cosph, const int* klon,
+                          const int* klat, const void* wlat, const void* cosphm1_ext, const void* depth_ext, const void* u_ext, const void* v_ext, void* dot,
+                          void* stream) {
+  if (!c) return fail("null context");
+  if (icase != 1 && icase != 2) return fail("ecwam_hip_propags_dot: ICASE must be 1 (spherical) or 2 (Cartesian)");
+  if (n < 0 || nland < n) return fail("ecwam_hip_propags_dot: bad range");
+  if (n > 0 && (!kxlt || !zdello || !cosph || !klon || !klat || !wlat || (icase == 1 && !cosphm1_ext) || !depth_ext || !u_ext || !v_ext || !dot))
+    return fail("ecwam_hip_propags_dot: null pointer");
+  if ((uintptr_t)dot % 16) return fail("ecwam_hip_propags_dot: dot must be 16-byte aligned");
+  const AdvGeom g{kxlt, zdello, xdella, cosph, nullptr, klon, klat, nullptr, wlat, nullptr, nullptr, cosphm1_ext, 0};
+  in_precision(c, [&](auto t) { launch_propags_dot<decltype(t)>(c->dtab, n, nland, c->p.irefra, icase, g, depth_ext, u_ext, v_ext, dot, (hipStream_t)stream); });
+  return launched();
+}
+
+int ecwam_hip_propags(ecwam_hip_ctx* c, const void* f1, void* f3, int n, int nland, int ngy, double delpro, double delphi, int flags, const int* kxlt,
+                      const void* cosph, const void* sinph, const void* dellam1_ext, const void* cosphm1_ext, const int* klon, const int* klat, const void* wlat,
+                      const void* cgroup_ext, const void* omosnh2kd_ext, const void* wavnum_ext, const void* u_ext, const void* v_ext, const void* dot, int kijs,
+                      int kijl, int copy_rest, void* cfl, int* cflfail, void* stream) {
+  if (!c) return fail("null context");
+  if (flags & ~(ECWAM_HIP_PROPAGS_CARTESIAN | ECWAM_HIP_PROPAGS_IRREGULAR)) return fail("ecwam_hip_propags: unknown flag bits");
+  if (!(delpro == std::floor(delpro)) || delpro < 0) return fail("ecwam_hip_propags: delpro must be a whole number of seconds (DELPRO = REAL(IDELPRO))");
+  if (!(delphi > 0)) return fail("ecwam_hip_propags: delphi must be positive");
+  const int vec = 16 / c->real_bytes;
+  if (c->NFRE % vec != 0) return fail("ecwam_hip_propags: NFRE is no whole number of 16-byte pieces");
+  if (kijs < 0 || kijl < kijs || kijl > n || nland < n) return fail("ecwam_hip_propags: bad range");
+  if (kijl == kijs) return 0;
+  const bool cart = flags & ECWAM_HIP_PROPAGS_CARTESIAN;
+  const int irefra = c->p.irefra;
+  const bool cur = irefra == 2 || irefra == 3;
+  if (!f1 || !dellam1_ext || !klon || !klat || !cgroup_ext || (!cart && (!kxlt || !cosph || !sinph || !cosphm1_ext || !wlat)))
+    return fail("ecwam_hip_propags: null pointer");
+  if (irefra != 0 && !dot) return fail("ecwam_hip_propags: IREFRA /= 0 needs the dot terms of ecwam_hip_propags_dot (dot is NULL)");
+  if (irefra != 0 && !omosnh2kd_ext) return fail("ecwam_hip_propags: IREFRA /= 0 needs OMOSNH2KD_EXT");
+  if (cur && (!wavnum_ext || !u_ext || !v_ext)) return fail("ecwam_hip_propags: IREFRA 2, 3 need WAVNUM_EXT, U_EXT and V_EXT");
+  if (!f3 && (cart || (!cfl && !cflfail))) return fail("ecwam_hip_propags: nothing to do (f3 is NULL and the call has no check to make)");
+  if (f1 == f3) return fail("ecwam_hip_propags: F1 and F3 must not alias");
+  if ((uintptr_t)f1 % 16 || (uintptr_t)f3 % 16 || (uintptr_t)cgroup_ext % 16 || (uintptr_t)omosnh2kd_ext % 16 || (uintptr_t)wavnum_ext % 16 || (uintptr_t)dot % 16)
+    return fail("ecwam_hip_propags: f1, f3, the rows of frequencies and dot must be 16-byte aligned");
+  if ((uintptr_t)cfl % c->real_bytes || (uintptr_t)cflfail % sizeof(int)) return fail("ecwam_hip_propags: cfl or cflfail misaligned");
+  if (c->obs && !cart && kijl > c->n_obs) return fail("ecwam_hip_propags: more points than the obstruction table holds");
+  PropagsCall a{f1, f3, nland, cart ? 2 : 1, (flags & ECWAM_HIP_PROPAGS_IRREGULAR) ? 1 : 0, irefra, delpro, delphi, kxlt, cosph, sinph, dellam1_ext, cosphm1_ext,
+                klon, klat, wlat, cgroup_ext, omosnh2kd_ext, wavnum_ext, u_ext, v_ext, irefra != 0 ? dot : nullptr, cart ? nullptr : c->obs, kijs, kijl,
+                copy_rest ? 1 : 0, cfl, cflfail};
+  (void)ngy;
+  const int rc = in_precision(c, [&](auto t) { return launch_propags<decltype(t)>(c->dtab, a, c->NFRE, (hipStream_t)stream); });
+  if (rc) return fail("ecwam_hip_propags: the tile of this NANG x NFRE does not fit the LDS (no build serves the configuration)");
+  return launched();
+}
+
 // The variant of k_implsch4 (implsch_v4.h; launch.h: Implsch4Variant) a context runs.  The common builds (implsch4.hip): flag sets A and B
 // (LLGCBZ0, LLNORMAGAM), with or without the sea-ice damping rates that depend on the frequency only (LCIWA1, LCIWA3, LCISCAL).  The alternate
 // builds (implsch4x.hip), on flag set A only: IPHYS 0 (sinput_jan + sdissip_jan; its TAUWSHELTER is 0), ISNONLIN 1 (TRANSF per interaction

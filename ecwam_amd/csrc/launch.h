@@ -13,6 +13,7 @@
 #include "../../include/ecwam_hip_readwind.h"
 #include "../../include/ecwam_hip_restart.h"
 #include "../../include/ecwam_hip_gribin.h"
+#include "../../include/ecwam_hip_propags.h"
 #include "../../include/ecwam_hip_gribout.h"
 #include "implsch_adv_args.h"
 
@@ -50,6 +51,25 @@ template <typename T> void launch_p2c(const void* pt, void* ch, int nproma, int 
 template <typename T> void launch_pack(const void* fl, const int* idx, int n, int rowlen, void* buf, hipStream_t s);
 template <typename T> void launch_proenv_pack(int n, int NFRE, const void* wvprpt, const void* om, const void* depth, const void* u, const void* v, void* buf, hipStream_t s);
 template <typename T> void launch_proenv_unpack(int nrows, int NFRE, const void* buf, const void* land, void* wn, void* cg, void* om, void* dep, void* u, void* v, hipStream_t s);
+
+// ---- propags.hip: the first-order scheme, IPROPAGS = 0 (include/ecwam_hip_propags.h).  launch_propags: 0 = launched (or nothing to do), 1 = the tile does not
+// fit the LDS; f3 == nullptr: CHECKCFL alone -----------------------------------------------------------------------------------------------------------------
+struct PropagsCall {
+  const void *f1;
+  void* f3;
+  int nland, icase, irgg, irefra;
+  double delpro, delphi;
+  const int* kxlt;
+  const void *cosph, *sinph, *dellam1, *cosphm1;
+  const int *klon, *klat;
+  const void *wlat, *cg, *om, *wn, *u, *v, *dot, *obs;
+  int kijs, kijl, copy_rest;
+  void* cfl;
+  int* cflfail;
+};
+template <typename T> void launch_propags_dot(const void* tab, int n, int nland, int irefra, int icase, const AdvGeom& g, const void* depth, const void* ue, const void* ve, void* dot,
+        hipStream_t s);
+template <typename T> int launch_propags(const void* tab, const PropagsCall& c, int NFRE, hipStream_t s);
 
 // ---- implsch4.hip, implsch4x.hip, implsch4r.hip, implsch4a.hip, implsch4w.hip: the launchers of k_implsch4 (implsch_v4.h) ------------------------------
 // The kernel is built at the spectral shapes of implsch_v4_shapes.h, in the variants below; one translation unit per group of variants (they

@@ -136,6 +136,17 @@ class DepthOpts(C.Structure):
     _fields_ = [("dkmax", C.c_double), ("gam_b_j", C.c_double)]
 
 
+# include/ecwam_hip_propags.h: the first-order propagation scheme (IPROPAGS = 0: PROPAGS, CHECKCFL, PROPDOT with GRADI), added to ABI 6 in the same way
+EXPORTS_PROPAGS = ["ecwam_hip_propags_dot", "ecwam_hip_propags"]
+PROPAGS_CARTESIAN, PROPAGS_IRREGULAR = 1, 2
+PROPAGS_NCFL = 11      # DTC, CFLEA, CFLWE, CFLNO, CFLSO, CFLNO2, CFLSO2, CFLTP, CFLTM, CFLOP, CFLOM
+
+
+def propags_dot_width(nang: int) -> int:
+    """ECWAM_HIP_PROPAGS_DOT_W: THDD(K), THDC(K), S0(K), OMDD, three reals of padding"""
+    return 3 * nang + 4
+
+
 ABI_VERSION = 6        # include/ecwam_hip.h ECWAM_HIP_ABI_VERSION
 _lib = None
 
@@ -267,6 +278,10 @@ def load() -> C.CDLL:
     lib.ecwam_hip_savstress_pack.argtypes = [vp, ci, ci, vp, vp, vp, ci, vp, ci, vp]
     lib.ecwam_hip_getstress_unpack.argtypes = [vp, ci, ci, vp, ci, ci, vp, vp, vp, vp]
     lib.ecwam_hip_savspec_pack.argtypes = [vp, ci, ci, vp, ci, ci, ci, vp, ci, vp]
+    for name in EXPORTS_PROPAGS:
+        getattr(lib, name).restype = C.c_int
+    lib.ecwam_hip_propags_dot.argtypes = [vp, ci, ci, ci, vp, vp, cd, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.ecwam_hip_propags.argtypes = [vp, vp, vp, ci, ci, ci, cd, cd, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, vp, vp, vp]
     _lib = lib
     return lib
 

@@ -117,7 +117,16 @@ class Wamintgr:
 
     def __init__(self, cfg: Config, grid, prec: str = "sp", device: int = 0, rank: int = 0, nranks: int = 1,
                  ifrelfmax: int = 0, delpro_lf: float | None = None, weights: str = "otf", strip_width: int = 0,
-                 halo_transport: str = "torch"):
+                 halo_transport: str = "torch", ipropags: int = 2):
+        # ipropags: the propagation scheme of PROPAG_WAM (propag_wam.F90:217-363).  2 = PROPAGS2, the corner-transport scheme (every path below);
+        # 0 = PROPAGS, the first-order upwind scheme with CHECKCFL (HipContext.propags).  1 (PROPAGS1) is not served.
+        if ipropags not in (0, 2):
+            raise ValueError("ipropags must be 0 (PROPAGS) or 2 (PROPAGS2); IPROPAGS = 1 is not served")
+        if ipropags == 0 and ifrelfmax > 0:
+            raise ValueError("ipropags = 0 has no fast-wave sub-steps: PROPAG_WAM sub-steps only in CASE(2) (ifrelfmax must be 0)")
+        if ipropags == 0 and weights == "stored":
+            raise ValueError("ipropags = 0 has no stored weights: PROPAGS forms its weights in every call (weights must be 'otf')")
+        self.ipropags = ipropags
         # weights: "otf" rebuilds the CTU weights inside PROPAGS2 (no W array, default); "stored" keeps the reference's
         # scheme (CTUW once into W[ij][8][NANG*NFRE_RED], PROPAGS2 streams them).  Bit-identical results.
         self.cfg, self.grid, self.prec = cfg, grid, prec
@@ -147,7 +156,7 @@ class Wamintgr:
         elif strip_width < 0:      # 2-D tiles of four latitude rows x four longitudes
             self.order = torch.from_numpy(decomp.tile2d_order(grid, self.dom)).to(self.dev)
             self.tiles2d = True
-        if self.order is not None and (int(cfg.irefra) or weights == "stored"):
+        if self.order is not None and (int(cfg.irefra) or weights == "stored" or ipropags == 0):
             # the refraction and stored-weight kernels walk the rows in their natural order: a work order (whose padded length would
             # otherwise replace the row range handed to them) does not apply
             self.order, self.tiles2d = None, False
@@ -189,6 +198,14 @@ class Wamintgr:
             self.v_ext = torch.zeros(self.nrows, **z)
             self.omosnh2kd_ext = torch.zeros((self.nrows, NFRE), **z)
             self.wavnum_ext = torch.zeros((self.nrows, NFRE), **z)
+        if ipropags == 0:
+            # DELLAM1_EXT = 1 / DELLAM(KXLT) of the owned and the halo rows, DELLAM = ZDELLO CIRC / 360 (readmdlconf.F90:145, mpdecomp.F90:1428); land slot 0
+            T = self.npdt
+            dellam = np.asarray(grid.zdello, T) * T(self.t.CIRC) / T(360.0)
+            d1 = np.zeros(self.nrows, T)
+            d1[:self.dom.nland] = T(1) / dellam[np.asarray(grid.kxlt)[self.dom.ext_global()]]
+            self.gd = dict(self.gd, dellam1_ext=torch.from_numpy(d1).to(self.dev))
+            self.dot = torch.zeros((self.n, 3 * NANG + 4), **z) if self.irefra else None
 
     @property
     def fast_mode(self) -> str:
@@ -307,6 +324,13 @@ class Wamintgr:
     def build_weights(self) -> int:
         c = self.cfg
         self.cflfail.zero_()
+        if self.ipropags == 0:
+            # PROPDOT with refraction (propag_wam.F90:343-350), then CHECKCFL as PROPAGS calls it, without a spectrum written
+            if self.irefra:
+                self.ctx.propags_dot(self.gd, self.depth_ext, self.u_ext, self.v_ext, self.dot)
+            self.ctx.propags(self.fl1, None, self.gd, self.cgroup_ext, float(c.idelpro), 0, self.n, cflfail=self.cflfail, **self._propags_env())
+            self.weights_ready = True
+            return int(self.cflfail.sum().item())
         if self.irefra:
             # PROPDOT, then CTUWINI + CTUWDRV per frequency range (checks only: the weights are rebuilt inside PROPAGS2)
             self.ctx.propdot(self.gd, self.depth_ext, self.u_ext, self.v_ext, self.refr)
@@ -329,6 +353,12 @@ class Wamintgr:
         self.weights_ready = True
         return int(self.cflfail.sum().item())
 
+    def _propags_env(self) -> dict:
+        """what HipContext.propags reads beside CGROUP_EXT at the context's IREFRA"""
+        if not self.irefra:
+            return {}
+        return dict(omosnh2kd_ext=self.omosnh2kd_ext, wavnum_ext=self.wavnum_ext, u_ext=self.u_ext, v_ext=self.v_ext, dot=self.dot)
+
     def _halo_finish_timed(self, reqs) -> None:
         """halo.finish between two events on the compute stream when the caller collects them (bench.py: what the overlap did not hide)."""
         if self.halo_events is None:
@@ -340,17 +370,21 @@ class Wamintgr:
         e1.record()
         self.halo_events.append((e0, e1))
 
-    # ---- PROPAG_WAM (propag_wam.F90:166-313), IPROPAGS = 2
+    # ---- PROPAG_WAM (propag_wam.F90:166-313), IPROPAGS = 2; (propag_wam.F90:341-362), IPROPAGS = 0
     def propag(self) -> None:
         if not self.weights_ready:
             nfail = self.build_weights()
             if nfail:
-                raise api.EcwamHipError(f"CFL criterion violated at {nfail} points (ctuwdrv.F90:128-146)")
+                where = "checkcfl.F90:74-247" if self.ipropags == 0 else "ctuwdrv.F90:128-146"
+                raise api.EcwamHipError(f"CFL criterion violated at {nfail} points ({where})")
         c, g = self.cfg, self.gd
         lf = 0 < self.ifrelfmax < c.nfre_red
 
         def advect_rows(k0, k1, m1, m2, delpro, copy_rest, split=0, src=None):
             if k1 <= k0:
+                return
+            if self.ipropags == 0:
+                self.ctx.propags(self.fl1, self.fl3, g, self.cgroup_ext, delpro, k0, k1, copy_rest=copy_rest, **self._propags_env())
                 return
             tiled = self.tiles2d and (k0, k1) == (0, self.n)
             if tiled:                                        # the range indexes the entries of the (padded) tile order
@@ -512,6 +546,8 @@ class Wamintgr:
         on-the-fly weights in the natural row order, with or without sub-grid obstructions; fast-wave sub-steps run on compact rows (the
         last one inside the kernel)."""
         lf = 0 < self.ifrelfmax < self.cfg.nfre_red
+        if self.ipropags != 2:      # the one-kernel step advects with PROPAGS2
+            return False
         return (self.ctx.fused_supported(fast_waves=lf, obstructions=self.ctx.has_obstructions) and not self.irefra and self.weights == "otf"
                 and self.order is None and (not lf or (self.g1 is not None and self.fast_mode == "compact")))
 
