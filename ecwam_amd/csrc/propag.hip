@@ -682,6 +682,16 @@ __device__ __forceinline__ bool ctu_wgen(const CtuBase<T>& b, T sink, T cosk, co
   return fail;
 }
 
+// `neg` of ctu_fast_wgen (ctu.h) for one frequency alone: the same four numbers, formed the same way
+template <typename T>
+__device__ __forceinline__ bool ctu_fast_neg(T xa, T xb, T ya, T yb, T asink, T acosk, T su, T sva, T svb) {
+#pragma clang fp contract(off)
+  typedef CtuV2<T> F;
+  const F adx = ctu_v2fma<T>(F{xa, xb}, F{asink, asink}, F{su, su});
+  const F ady = ctu_v2fma<T>(F{ya, yb}, F{acosk, acosk}, F{sva, svb});
+  return m_min(m_min(adx.x, adx.y), m_min(ady.x, ady.y)) < T(0);
+}
+
 // PROPAGS2 for IREFRA = 1, 2, 3 with the weights rebuilt on the fly (and, with f1 == nullptr, the CFL / range checks of
 // CTUW alone: cflfail[ij] = 1 where one fails).  Same tile structure as k_propags2_otf: a thread owns VW consecutive
 // frequencies of one (point, direction) and moves 16 bytes per access.
@@ -894,6 +904,14 @@ __global__ void __launch_bounds__(256) k_propags2_gen(const DevTab<T>* __restric
           fw[c / 2] = ctu_fast_wgen<T>(P2(xa), P2(xb), P2(ya), P2(yb), m_abs(sink), m_abs(cosk), su, sva, svb, p.zd, xdella, p.ga, e[0], e[1], p.wl[jy0],
                                        e[2 + jy0], p.wc[kc[0]], e[4 + kc[0]], P2(dthp_), P2(dthm_), P2(fdp_), P2(fdm_), FRATIO, rfr, n_);
           neg |= n_;
+        }
+        if (VW == 1) {
+          // The form of the arithmetic is chosen per aligned PAIR of frequencies in every build: the scalar build asks its partner too, as the
+          // two-frequency build does by construction.  F3 then does not depend on the build the bounds and the alignment select.
+          const int d = (m & 1) ? -1 : 1;
+          if (m + d < NR)
+            neg |= ctu_fast_neg<T>(bf[jx0 * NFRE + d], bf[(1 - jx0) * NFRE + d], bf[(2 + jy0) * NFRE + d], bf[(3 - jy0) * NFRE + d], m_abs(sink), m_abs(cosk),
+                                   su, sva, svb);
         }
         if (!neg) {
           const T* fo = f1 + own;

@@ -21,6 +21,7 @@ or where a fixture cannot be recorded with the reference's (a finding about the 
   YOWGRIB           intake    the reference's is bound to GRIB_API; INITIALINT imports one name and calls nothing
   YOWGRIB           gribout   the same: WGRIBENCODE_VALUES imports three names it does not use on this path
   OML_MOD           gribout   another package (fiat); one name, used by this driver alone
+  OML_MOD           ctu       the same package; CTUWDRV calls its one function, which answers 1 thread here (one block of all points)
   MPL_MODULE        intake    another package (fiat); one name (MPL_COMM), used by this driver alone
   MPL_DATA_MODULE   intake    the same
   YOWWIND           forcing   the reference's RWFAC is a PARAMETER (0.5); the recorded GETWND cases weigh the current with 1 and 0.625

@@ -367,18 +367,20 @@ def tables_of(T, nang=NANG, nfre=NFRE, nfre_red=NFRE_RED, irefra=0):
     return Tables(Config(nang=nang, nfre=nfre, nfre_red=nfre_red, irefra=irefra), T)
 
 
-def make_inputs(T, g, t, icase, irgg, irefra, with_obs, idelpro, seed=7):
+def make_inputs(T, g, t, icase, irgg, irefra, with_obs, idelpro, seed=7, depth_lo=4.0, cur_amp=1.5, obscor=False):
     """The arguments of dot_terms and propags for grid g and tables t, in the working precision T.  Every field is rounded to single precision first; what
-    the reference derives (DELPHI, DELLAM, 1 / DELLAM, 1 / COSPH) is derived here in T, as readmdlconf.F90:136, 145 and mpdecomp.F90:1428-1429 do."""
+    the reference derives (DELPHI, DELLAM, 1 / DELLAM, 1 / COSPH) is derived here in T, as readmdlconf.F90:136, 145 and mpdecomp.F90:1428-1429 do.
+    depth_lo: the shallowest depth drawn; cur_amp: the largest current component; obscor: the planes OBSCOR(1:4) of `obs` are drawn too (they are 1 otherwise:
+    the first-order scheme has no corner points).  The defaults are the inputs of the recorded propags_* cases."""
     from ecwam_amd import synthetic as syn
 
     rng = np.random.default_rng(seed)
     n, nland, nrow = g.nsea, g.nland, g.nsea + 1
     nang, nfre, nr = t.cfg.nang, t.cfg.nfre, t.cfg.nfre_red
-    depth = _f32(np.where(rng.uniform(size=nrow) < 0.5, rng.uniform(4.0, 40.0, nrow), rng.uniform(40.0, 400.0, nrow)))
+    depth = _f32(np.where(rng.uniform(size=nrow) < 0.5, rng.uniform(depth_lo, 40.0, nrow), rng.uniform(40.0, 400.0, nrow)))
     depth[nland] = 999.0
-    u = _f32(rng.uniform(-1.5, 1.5, nrow))
-    v = _f32(rng.uniform(-1.5, 1.5, nrow))
+    u = _f32(rng.uniform(-cur_amp, cur_amp, nrow))
+    v = _f32(rng.uniform(-cur_amp, cur_amp, nrow))
     undefined = rng.choice(n, 4, replace=False)      # an exact zero: the current is not defined there
     u[undefined] = v[undefined] = 0.0
     u[nland] = v[nland] = 0.0
@@ -390,6 +392,8 @@ def make_inputs(T, g, t, icase, irgg, irefra, with_obs, idelpro, seed=7):
     if with_obs:
         obs = np.ones((n, 8, nfre))
         obs[:, :4] = _f32(rng.uniform(0.3, 0.95, (n, 4, nfre)))
+        if obscor:      # drawn after the four planes above, which keep their values
+            obs[:, 4:] = _f32(rng.uniform(0.3, 0.95, (n, 4, nfre)))
         obs = obs.astype(T)
     zdello, cosph, sinph = _f32(g.zdello).astype(T), _f32(g.cosph).astype(T), _f32(g.sinph).astype(T)
     xdella = float(_f32(g.xdella))

@@ -17,7 +17,7 @@ from oracle import ref_build  # noqa: E402
 
 # the tool -> what its fixture files begin with
 TOOLS = {"forcing": "forcing_", "intake": "intake_", "restart": "restart_", "readwind": "readwind_", "start": "start_", "gribout": "gribout_",
-         "gribin": "gribin_", "nest": "intspec_"}
+         "gribin": "gribin_", "nest": "intspec_", "ctu": "ctu_"}
 
 
 @pytest.mark.parametrize("tool", list(TOOLS))
