@@ -330,6 +330,51 @@ class HipContext:
             opt(v_ext, (nrow,), "V_EXT"), opt(dot, (n, _lib.propags_dot_width(self.NANG)), "DOT"), kijs, kijl, int(bool(copy_rest)),
             opt(cfl, (n, self.NANG, _lib.PROPAGS_NCFL), "CFL"), None if cflfail is None else self._int(cflfail, (n,), "CFLFAIL"), _stream_ptr()))
 
+    # -- IPROPAGS = 1: PROPAGS1 with CHECKCFL (propag_wam.F90:296-322; include/ecwam_hipx_propags1.h)
+    @property
+    def has_rotated(self) -> bool:
+        return getattr(self, "_rot", None) is not None
+
+    def set_rotated(self, tables) -> None:
+        """tables: device tensors krlat, krlon [n][2][2] (int32), wrlat, wrlon [n][2], cdr, sdr [nrow][NANG], prqrt [n] and the number sqrt2 (the dict of
+        rotated_to_device); None switches them off.  The tensors are kept alive here."""
+        if tables is None:
+            self._rot = None
+            self._chk(self.lib.ecwam_hipx_set_rotated(self._h, 0, 0, None, None, None, None, None, None, None, 0.0))
+            return
+        t = tables
+        n, nrow = t["prqrt"].shape[0], t["cdr"].shape[0]
+        self._chk(self.lib.ecwam_hipx_set_rotated(
+            self._h, n, nrow, self._int(t["krlat"], (n, 2, 2), "KRLAT"), self._int(t["krlon"], (n, 2, 2), "KRLON"), self._real(t["wrlat"], (n, 2), "WRLAT"),
+            self._real(t["wrlon"], (n, 2), "WRLON"), self._real(t["cdr"], (nrow, self.NANG), "CDR"), self._real(t["sdr"], (nrow, self.NANG), "SDR"),
+            self._real(t["prqrt"], (n,), "PRQRT"), float(t["sqrt2"])))
+        self._rot = dict(t)
+
+    def propags1(self, f1, f3, grid_dev: dict, cgroup_ext, delpro: float, kijs, kijl, omosnh2kd_ext=None, wavnum_ext=None, u_ext=None, v_ext=None, dot=None,
+                 copy_rest=True, cfl=None, cflfail=None, icase: int = 1, irgg: int = 1, delphi: float | None = None):
+        """PROPAGS1 for rows [kijs, kijl): the arguments of propags; on a spherical grid with IREFRA 0 or 1 the tables of set_rotated are read."""
+        g = grid_dev
+        n, nland, ngy = g["n"], g["nland"], g["ngy"]
+        nrow = f1.shape[0]
+        if nland >= nrow or cgroup_ext.shape[0] != nrow:
+            raise ValueError("PROPAGS1: F1 / CGROUP_EXT without the land row")
+        npdt = np.float32 if self.dtype == torch.float32 else np.float64
+        if delphi is None:
+            delphi = float(npdt(g["xdella"]) * npdt(self.t.CIRC) / npdt(360.0))
+
+        def opt(t, shape, name):
+            return None if t is None else self._real(t, shape, name)
+
+        flags = (_lib.PROPAGS_CARTESIAN if icase == 2 else 0) | (_lib.PROPAGS_IRREGULAR if irgg == 1 else 0)
+        self._chk(self.lib.ecwam_hipx_propags1(
+            self._h, self._real(f1, (nrow, self.NANG, self.NFRE), "F1"), opt(f3, (nrow, self.NANG, self.NFRE), "F3"), n, nland, ngy, float(delpro), float(delphi),
+            flags, self._int(g["kxlt"], (n,), "KXLT"), self._real(g["cosph"], (ngy,), "COSPH"), self._real(g["sinph"], (ngy,), "SINPH"),
+            self._real(g["dellam1_ext"], (nrow,), "DELLAM1_EXT"), self._real(g["cosphm1_ext"], (nrow,), "COSPHM1_EXT"), self._int(g["klon"], (n, 2), "KLON"),
+            self._int(g["klat"], (n, 2, 2), "KLAT"), self._real(g["wlat"], (n, 2), "WLAT"), self._real(cgroup_ext, (nrow, self.NFRE), "CGROUP_EXT"),
+            opt(omosnh2kd_ext, (nrow, self.NFRE), "OMOSNH2KD_EXT"), opt(wavnum_ext, (nrow, self.NFRE), "WAVNUM_EXT"), opt(u_ext, (nrow,), "U_EXT"),
+            opt(v_ext, (nrow,), "V_EXT"), opt(dot, (n, _lib.propags_dot_width(self.NANG)), "DOT"), kijs, kijl, int(bool(copy_rest)),
+            opt(cfl, (n, self.NANG, _lib.PROPAGS_NCFL), "CFL"), None if cflfail is None else self._int(cflfail, (n,), "CFLFAIL"), _stream_ptr()))
+
     # -- IMPLSCH (implsch.F90:10-23)
     def implsch(self, kijs, kijl, fl1, wvprpt, ff, intf, mij, xllws, dbg=None, wam2nemo=None):
         nrow = fl1.shape[0]
@@ -1250,6 +1295,15 @@ def propags_grid(grid_dev: dict, grid, circ) -> dict:
     d = np.zeros(ref.shape[0], T)
     d[:grid.nsea] = T(1) / dellam[grid.kxlt]
     return dict(grid_dev, dellam1_ext=torch.from_numpy(d).to(ref.device))
+
+
+def rotated_to_device(tables: dict, dtype, device) -> dict:
+    """The tables of grid.rotated_tables as the device tensors HipContext.set_rotated takes."""
+    npdt = np.float32 if dtype == torch.float32 else np.float64
+    out = {k: torch.from_numpy(np.ascontiguousarray(tables[k], dtype=np.int32)).to(device) for k in ("krlat", "krlon")}
+    out.update({k: torch.from_numpy(np.ascontiguousarray(tables[k], dtype=npdt)).to(device) for k in ("wrlat", "wrlon", "cdr", "sdr", "prqrt")})
+    out["sqrt2"] = float(npdt(tables["sqrt2"]))
+    return out
 
 
 def grid_to_device(grid, dtype, device, lo: int = 0, hi: int | None = None, local=None) -> dict:

@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libecwam_hip.so")
-SOURCES = ["capi.hip", "propag.hip", "implsch4.hip", "implsch4a.hip", "implsch4x.hip", "implsch4r.hip", "implsch4rd.hip", "implsch4w.hip", "outbs.hip", "outbs_sep.hip", "outbs_ext.hip", "outbs_fl2nd.hip", "outbs_2nd.hip", "outbs_int.hip", "outblock.hip", "nest.hip", "start.hip", "forcing.hip", "intake.hip", "readwind.hip", "gribout.hip", "gribin.hip", "restart.hip", "propags.hip"]
+SOURCES = ["capi.hip", "propag.hip", "implsch4.hip", "implsch4a.hip", "implsch4x.hip", "implsch4r.hip", "implsch4rd.hip", "implsch4w.hip", "outbs.hip", "outbs_sep.hip", "outbs_ext.hip", "outbs_fl2nd.hip", "outbs_2nd.hip", "outbs_int.hip", "outblock.hip", "nest.hip", "start.hip", "forcing.hip", "intake.hip", "readwind.hip", "gribout.hip", "gribin.hip", "restart.hip", "propags.hip", "propags1.hip"]
 # objects that are a second compilation of another source: object name -> (source, extra flags; a later -O overrides the earlier one).
 # implsch4r / implsch4rd = the single / double precision RARE builds of k_implsch4 (double precision: the two-kernel split, implsch4r.hip)
 DERIVED = {"implsch4r.hip": ("implsch4r.hip", ["-DV4R_PREC=1"]), "implsch4rd.hip": ("implsch4r.hip", ["-DV4R_PREC=2"])}

@@ -119,6 +119,7 @@ struct ecwam_hip_ctx {
   void* gmap_keys = nullptr;
   const void* obs = nullptr;  // LSUBGRID: device OBS[n_obs][8][NFRE] (ecwam_hip_set_obstructions), read by CTUW / PROPAGS2
   int n_obs = 0;
+  RotatedTables rot;          // IPROPAGS = 1: the device tables of ecwam_hipx_set_rotated, read by ecwam_hipx_propags1
 };
 
 static void grib_map_free(ecwam_hip_ctx* c) {
@@ -811,6 +812,70 @@ int ecwam_hip_propags(ecwam_hip_ctx* c, const void* f1, void* f3, int n, int nla
   (void)ngy;
   const int rc = in_precision(c, [&](auto t) { return launch_propags<decltype(t)>(c->dtab, a, c->NFRE, (hipStream_t)stream); });
   if (rc) return fail("ecwam_hip_propags: the tile of this NANG x NFRE does not fit the LDS (no build serves the configuration)");
+  return launched();
+}
+
+// ---- IPROPAGS = 1: the dual rotated-quadrant scheme (include/ecwam_hipx_propags1.h; csrc/propags1.hip, and csrc/propags.hip for sections 1, 2, 4) ----------
+int ecwam_hipx_set_rotated(ecwam_hip_ctx* c, int n, int nrow, const int* krlat, const int* krlon, const void* wrlat, const void* wrlon, const void* cdr,
+                           const void* sdr, const void* prqrt, double sqrt2) {
+  if (!c) return fail("null context");
+  const int given = (krlat != nullptr) + (krlon != nullptr) + (wrlat != nullptr) + (wrlon != nullptr) + (cdr != nullptr) + (sdr != nullptr) + (prqrt != nullptr);
+  if (given == 0) {
+    c->rot = RotatedTables{};
+    return 0;
+  }
+  if (given != 7) return fail("ecwam_hipx_set_rotated: some tables are NULL and others are not");
+  if (n < 0 || nrow <= n) return fail("ecwam_hipx_set_rotated: bad size (nrow <= n: CDR and SDR cover the rows of the neighbours too)");
+  if (!(sqrt2 > 0)) return fail("ecwam_hipx_set_rotated: sqrt2 must be positive");
+  if ((uintptr_t)krlat % sizeof(int) || (uintptr_t)krlon % sizeof(int) || (uintptr_t)wrlat % c->real_bytes || (uintptr_t)wrlon % c->real_bytes ||
+      (uintptr_t)cdr % c->real_bytes || (uintptr_t)sdr % c->real_bytes || (uintptr_t)prqrt % c->real_bytes)
+    return fail("ecwam_hipx_set_rotated: a table is misaligned");
+  c->rot.n = n; c->rot.nrow = nrow;
+  c->rot.krlat = krlat; c->rot.krlon = krlon;
+  c->rot.wrlat = wrlat; c->rot.wrlon = wrlon; c->rot.cdr = cdr; c->rot.sdr = sdr; c->rot.prqrt = prqrt;
+  c->rot.sqrt2 = sqrt2;
+  return 0;
+}
+
+int ecwam_hipx_propags1(ecwam_hip_ctx* c, const void* f1, void* f3, int n, int nland, int ngy, double delpro, double delphi, int flags, const int* kxlt,
+                        const void* cosph, const void* sinph, const void* dellam1_ext, const void* cosphm1_ext, const int* klon, const int* klat, const void* wlat,
+                        const void* cgroup_ext, const void* omosnh2kd_ext, const void* wavnum_ext, const void* u_ext, const void* v_ext, const void* dot, int kijs,
+                        int kijl, int copy_rest, void* cfl, int* cflfail, void* stream) {
+  if (!c) return fail("null context");
+  if (flags & ~(ECWAM_HIPX_PROPAGS1_CARTESIAN | ECWAM_HIPX_PROPAGS1_IRREGULAR)) return fail("ecwam_hipx_propags1: unknown flag bits");
+  if (!(delpro == std::floor(delpro)) || delpro < 0) return fail("ecwam_hipx_propags1: delpro must be a whole number of seconds (DELPRO = REAL(IDELPRO))");
+  if (!(delphi > 0)) return fail("ecwam_hipx_propags1: delphi must be positive");
+  const int vec = 16 / c->real_bytes;
+  if (c->NFRE % vec != 0) return fail("ecwam_hipx_propags1: NFRE is no whole number of 16-byte pieces");
+  if (kijs < 0 || kijl < kijs || kijl > n || nland < n) return fail("ecwam_hipx_propags1: bad range");
+  const bool cart = flags & ECWAM_HIPX_PROPAGS1_CARTESIAN;
+  const int irefra = c->p.irefra;
+  const bool cur = irefra == 2 || irefra == 3;
+  const bool rotated = !cart && !cur;      // section 3
+  if (rotated && !c->rot.krlat) return fail("ecwam_hipx_propags1: a spherical grid with IREFRA 0 or 1 needs the rotated tables (ecwam_hipx_set_rotated)");
+  if (rotated && (kijl > c->rot.n || nland > c->rot.nrow))
+    return fail("ecwam_hipx_propags1: the rotated tables hold fewer points or rows than the call reads");
+  if (kijl == kijs) return 0;
+  if (!f1 || !dellam1_ext || !klon || !klat || !cgroup_ext || (!cart && (!kxlt || !cosph || !sinph || !cosphm1_ext || !wlat)))
+    return fail("ecwam_hipx_propags1: null pointer");
+  if (irefra != 0 && !dot) return fail("ecwam_hipx_propags1: IREFRA /= 0 needs the dot terms of the first-order scheme's dot call (dot is NULL)");
+  if (irefra != 0 && !omosnh2kd_ext) return fail("ecwam_hipx_propags1: IREFRA /= 0 needs OMOSNH2KD_EXT");
+  if (cur && (!wavnum_ext || !u_ext || !v_ext)) return fail("ecwam_hipx_propags1: IREFRA 2, 3 need WAVNUM_EXT, U_EXT and V_EXT");
+  if (!f3 && (cart || (!cfl && !cflfail))) return fail("ecwam_hipx_propags1: nothing to do (f3 is NULL and the call has no check to make)");
+  if (f1 == f3) return fail("ecwam_hipx_propags1: F1 and F3 must not alias");
+  if ((uintptr_t)f1 % 16 || (uintptr_t)f3 % 16 || (uintptr_t)cgroup_ext % 16 || (uintptr_t)omosnh2kd_ext % 16 || (uintptr_t)wavnum_ext % 16 || (uintptr_t)dot % 16)
+    return fail("ecwam_hipx_propags1: f1, f3, the rows of frequencies and dot must be 16-byte aligned");
+  if ((uintptr_t)cfl % c->real_bytes || (uintptr_t)cflfail % sizeof(int)) return fail("ecwam_hipx_propags1: cfl or cflfail misaligned");
+  if (c->obs && !cart && kijl > c->n_obs) return fail("ecwam_hipx_propags1: more points than the obstruction table holds");
+  PropagsCall a{f1, f3, nland, cart ? 2 : 1, (flags & ECWAM_HIPX_PROPAGS1_IRREGULAR) ? 1 : 0, irefra, delpro, delphi, kxlt, cosph, sinph, dellam1_ext, cosphm1_ext,
+                klon, klat, wlat, cgroup_ext, omosnh2kd_ext, wavnum_ext, u_ext, v_ext, irefra != 0 ? dot : nullptr, cart ? nullptr : c->obs, kijs, kijl,
+                copy_rest ? 1 : 0, cfl, cflfail, 1};
+  (void)ngy;
+  const int rc = in_precision(c, [&](auto t) {
+    return rotated ? launch_propags1<decltype(t)>(c->dtab, a, c->rot, c->NANG, c->NFRE, (hipStream_t)stream)
+                   : launch_propags<decltype(t)>(c->dtab, a, c->NFRE, (hipStream_t)stream);
+  });
+  if (rc) return fail("ecwam_hipx_propags1: the tile of this NANG x NFRE does not fit the LDS (no build serves the configuration)");
   return launched();
 }
 

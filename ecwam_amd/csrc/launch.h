@@ -14,6 +14,7 @@
 #include "../../include/ecwam_hip_restart.h"
 #include "../../include/ecwam_hip_gribin.h"
 #include "../../include/ecwam_hip_propags.h"
+#include "../../include/ecwam_hipx_propags1.h"
 #include "../../include/ecwam_hip_gribout.h"
 #include "implsch_adv_args.h"
 
@@ -66,10 +67,21 @@ struct PropagsCall {
   int kijs, kijl, copy_rest;
   void* cfl;
   int* cflfail;
+  int dp_product = 0;      // section 4 alone: DP1, DP2 = DCO(IJ) * (1 / DCO(JH)) as propags1.F90:203-222 forms them, in place of the quotient of PROPAGS
 };
 template <typename T> void launch_propags_dot(const void* tab, int n, int nland, int irefra, int icase, const AdvGeom& g, const void* depth, const void* ue, const void* ve, void* dot,
         hipStream_t s);
 template <typename T> int launch_propags(const void* tab, const PropagsCall& c, int NFRE, hipStream_t s);
+
+// ---- propags1.hip: the dual rotated-quadrant scheme, IPROPAGS = 1 (include/ecwam_hipx_propags1.h): section 3 of PROPAGS1.  The tables are those of
+// ecwam_hipx_set_rotated: KRLAT, KRLON [n][2][2], WRLAT, WRLON [n][2], CDR, SDR [nrow][NANG], PRQRT [n].  Same return values as launch_propags ------------------
+struct RotatedTables {
+  int n = 0, nrow = 0;
+  const int *krlat = nullptr, *krlon = nullptr;
+  const void *wrlat = nullptr, *wrlon = nullptr, *cdr = nullptr, *sdr = nullptr, *prqrt = nullptr;
+  double sqrt2 = 0;
+};
+template <typename T> int launch_propags1(const void* tab, const PropagsCall& c, const RotatedTables& r, int NANG, int NFRE, hipStream_t s);
 
 // ---- implsch4.hip, implsch4x.hip, implsch4r.hip, implsch4a.hip, implsch4w.hip: the launchers of k_implsch4 (implsch_v4.h) ------------------------------
 // The kernel is built at the spectral shapes of implsch_v4_shapes.h, in the variants below; one translation unit per group of variants (they

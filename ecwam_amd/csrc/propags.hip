@@ -140,7 +140,8 @@ struct PropagsArgs {
 // the plane p of point t in the tile's LDS table of rows of frequencies
 #define PG_ROW(t, p) (sR + ((size_t)(t) * NPL + (p)) * NFRE)
 
-template <typename T, int VW, int SEC>
+// DPP (section 4 alone): DP1, DP2 as the product DCO(IJ) * (1 / DCO(JH)) of propags1.F90:203-222; the default is the quotient of propags.F90:217-224
+template <typename T, int VW, int SEC, bool DPP = false>
 __global__ void __launch_bounds__(256) k_propags(const DevTab<T>* __restrict__ tab, const PropagsArgs<T> a) {
 #pragma clang fp contract(off)
   extern __shared__ __align__(16) unsigned char pg_smem[];
@@ -176,8 +177,13 @@ __global__ void __launch_bounds__(256) k_propags(const DevTab<T>* __restrict__ t
       const T DCO = a.cosphm1[ij];
       const int j1 = q[PI_LAT11], j2 = q[PI_LAT21];
       s[PS_DCO] = DCO;
-      s[PS_DP1] = j1 == nland ? T(1) : DCO / a.cosphm1[j1];
-      s[PS_DP2] = j2 == nland ? T(1) : DCO / a.cosphm1[j2];
+      if (DPP) {
+        s[PS_DP1] = j1 == nland ? T(1) : DCO * (T(1) / a.cosphm1[j1]);
+        s[PS_DP2] = j2 == nland ? T(1) : DCO * (T(1) / a.cosphm1[j2]);
+      } else {
+        s[PS_DP1] = j1 == nland ? T(1) : DCO / a.cosphm1[j1];
+        s[PS_DP2] = j2 == nland ? T(1) : DCO / a.cosphm1[j2];
+      }
       const T w1 = a.wlat[ij * 2 + 0], w2 = a.wlat[ij * 2 + 1];
       s[PS_WL1] = w1; s[PS_WL2] = w2;
       s[PS_WM1] = T(1) - w1; s[PS_WM2] = T(1) - w2;
@@ -554,7 +560,10 @@ int launch_propags(const void* tab, const PropagsCall& c, int NFRE, hipStream_t 
     case 1: hipLaunchKernelGGL((k_propags<T, VW, 1>), grid, block, lds, s, tp, a); break;
     case 2: hipLaunchKernelGGL((k_propags<T, VW, 2>), grid, block, lds, s, tp, a); break;
     case 3: hipLaunchKernelGGL((k_propags<T, VW, 3>), grid, block, lds, s, tp, a); break;
-    default: hipLaunchKernelGGL((k_propags<T, VW, 4>), grid, block, lds, s, tp, a); break;
+    default:
+      if (c.dp_product) hipLaunchKernelGGL((k_propags<T, VW, 4, true>), grid, block, lds, s, tp, a);
+      else hipLaunchKernelGGL((k_propags<T, VW, 4>), grid, block, lds, s, tp, a);
+      break;
   }
   return 0;
 }

@@ -182,6 +182,75 @@ def build_grid(n: int, mask: str = "aqua", seed: int = 20230101, land_fraction: 
                 klat=klat.astype(np.int32), kcor=kcor.astype(np.int32), wlat=wlat, wcor=wcor, row_start=row_start)
 
 
+def _nint(x: np.ndarray) -> np.ndarray:
+    """NINT of a real array: round half away from zero, without forming |x| + 0.5 in the working precision."""
+    a = np.abs(x)
+    f = np.floor(a)
+    q = (f + (a - f >= 0.5)).astype(np.int64)
+    return np.where(x < 0, -q, q)
+
+
+def rotated_tables(g: Grid, T, sinth, costh) -> dict:
+    """The tables of the dual rotated-quadrant scheme (IPROPAGS = 1) for grid g, in the working precision T and the reference's order of operations:
+
+      KRLAT, KRLON [n][2][2]   (south, north) x (closest, second closest): KRLAT holds SE and NW, KRLON holds SW and NE (propconnect.F90:436-650), land = nland
+      WRLAT, WRLON [n][2]      the weight of the closest point (propconnect.F90:754-821, 893-961), IRGG = 1
+      CDR, SDR [n+1][NANG]     the advection speeds along SE-NW and SW-NE per unit group velocity, the land row 0 (mpdecomp.F90:1192-1241)
+      PRQRT [n], SQRT2         the fraction of the rotated grid (mpdecomp.F90:1242-1249) and 2 SIN(PI / 4) (propags1.F90:570)
+
+    ZDELLO, XDELLA and COSPH are g's, cast to T; NINT rounds half away from zero.  The grid is periodic (IPER = 1)."""
+    n, ngy = g.nsea, g.ngy
+    nlon = np.asarray(g.nlonrgg, np.int64)
+    k, i = g.kxlt.astype(np.int64), g.ixlg.astype(np.int64)
+    zdello, xdella, cosph = np.asarray(g.zdello).astype(T), T(g.xdella), np.asarray(g.cosph).astype(T)
+    off = np.concatenate([[0], np.cumsum(nlon)])
+    full2sea = np.full(int(off[-1]), n, np.int64)
+    full2sea[off[k] + i] = np.arange(n)
+    one, half, two = T(1), T(0.5), T(2)
+    twoxdella = two * xdella
+    d0 = i.astype(T) * zdello[k]
+    krlat, krlon = np.full((n, 2, 2), n, np.int64), np.full((n, 2, 2), n, np.int64)
+    wrlat, wrlon = np.ones((n, 2), T), np.ones((n, 2), T)
+    # SW -> KRLON(:,1,:), SE -> KRLAT(:,1,:), NW -> KRLAT(:,2,:), NE -> KRLON(:,2,:)
+    for dk, sx, ktab, wtab, ic in ((-1, -1, krlon, wrlon, 0), (-1, 1, krlat, wrlat, 0), (1, -1, krlat, wrlat, 1), (1, 1, krlon, wrlon, 1)):
+        kk = k + dk
+        ok = (kk >= 0) & (kk < ngy)
+        kr = np.clip(kk, 0, ngy - 1)
+        n2, zd2 = nlon[kr], zdello[kr]
+        xl = d0 - xdella if sx < 0 else d0 + xdella
+        xmin = xl / zd2
+        imin = _nint(xmin)      # 0-based
+        wrap = imin < 0 if sx < 0 else imin > n2 - 1
+        shift = n2 if sx < 0 else -n2
+        iminw = np.where(wrap, imin + shift, imin)
+        xminw = np.where(wrap, xmin + shift.astype(T), xmin).astype(T)
+        imin2 = np.where(xminw <= iminw.astype(T), np.maximum(iminw - 1, 0), np.minimum(iminw + 1, n2 - 1))
+        ktab[:, ic, 0] = np.where(ok, full2sea[off[kr] + np.clip(iminw, 0, n2 - 1)], n)
+        ktab[:, ic, 1] = np.where(ok, full2sea[off[kr] + imin2], n)
+        xp = imin.astype(T) * zd2      # the reference does not wrap XP
+        d4, d6 = xp - half * zd2, xp + half * zd2
+        lo, hi = (d0 - twoxdella, d0) if sx < 0 else (d0, d0 + twoxdella)
+        w_zd_l = np.minimum(one, (zd2 - (xp - xl)) / zd2)
+        w_2x_l = np.minimum(one, (twoxdella - (d4 - lo)) / twoxdella)
+        w_zd_r = np.minimum(one, (zd2 - (xl - xp)) / zd2)
+        w_2x_r = np.minimum(one, (twoxdella - (hi - d6)) / twoxdella)
+        left = np.where(d4 <= lo, one, np.where(d6 <= hi, w_zd_l, w_2x_l))
+        right = np.where(d6 >= hi, one, np.where(d4 >= lo, w_zd_r, w_2x_r))
+        wtab[:, ic] = np.where(ok, np.where(xl <= xp, left, right), one)
+    sinth, costh = np.asarray(sinth, T), np.asarray(costh, T)
+    sqrt2o2 = np.sin(T(0.25) * T(np.pi))
+    cdr, sdr = np.zeros((n + 1, sinth.size), T), np.zeros((n + 1, sinth.size), T)
+    cp = cosph[k]
+    a = sqrt2o2 * costh[None, :] * cp[:, None]
+    b = sqrt2o2 * sinth[None, :]
+    cdr[:n], sdr[:n] = a - b, a + b
+    thetamax = np.arctan2(one, cp)
+    delta = cp / (np.sin(thetamax) * (one + cp * cp))
+    prqrt = np.minimum(half, delta).astype(T)
+    return dict(krlat=krlat.astype(np.int32), krlon=krlon.astype(np.int32), wrlat=wrlat, wrlon=wrlon, cdr=cdr, sdr=sdr, prqrt=prqrt,
+                sqrt2=T(two * np.sin(T(0.25) * T(np.pi))))
+
+
 def nsea_aqua(n: int) -> int:
     """Sea-point count of the all-ocean O<n> grid (4N(N+9)-40)."""
     return 4 * n * (n + 9) - 40

@@ -147,6 +147,11 @@ def propags_dot_width(nang: int) -> int:
     return 3 * nang + 4
 
 
+# include/ecwam_hipx_propags1.h: the dual rotated-quadrant scheme (IPROPAGS = 1: PROPAGS1), added to ABI 6.  The list of names with the prefix ecwam_hip_ is held
+# closed by tests/test_propags_host.py: additions from here on take the prefix ecwam_hipx_ and are listed in an EXPORTS_X_* list
+EXPORTS_X_PROPAGS1 = ["ecwam_hipx_set_rotated", "ecwam_hipx_propags1"]
+
+
 ABI_VERSION = 6        # include/ecwam_hip.h ECWAM_HIP_ABI_VERSION
 _lib = None
 
@@ -282,6 +287,10 @@ def load() -> C.CDLL:
         getattr(lib, name).restype = C.c_int
     lib.ecwam_hip_propags_dot.argtypes = [vp, ci, ci, ci, vp, vp, cd, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.ecwam_hip_propags.argtypes = [vp, vp, vp, ci, ci, ci, cd, cd, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, vp, vp, vp]
+    for name in EXPORTS_X_PROPAGS1:
+        getattr(lib, name).restype = C.c_int
+    lib.ecwam_hipx_set_rotated.argtypes = [vp, ci, ci, vp, vp, vp, vp, vp, vp, vp, cd]
+    lib.ecwam_hipx_propags1.argtypes = lib.ecwam_hip_propags.argtypes
     _lib = lib
     return lib
 

@@ -117,15 +117,20 @@ class Wamintgr:
 
     def __init__(self, cfg: Config, grid, prec: str = "sp", device: int = 0, rank: int = 0, nranks: int = 1,
                  ifrelfmax: int = 0, delpro_lf: float | None = None, weights: str = "otf", strip_width: int = 0,
-                 halo_transport: str = "torch", ipropags: int = 2):
+                 halo_transport: str = "torch", ipropags: int = 2, rotated: dict | None = None):
         # ipropags: the propagation scheme of PROPAG_WAM (propag_wam.F90:217-363).  2 = PROPAGS2, the corner-transport scheme (every path below);
-        # 0 = PROPAGS, the first-order upwind scheme with CHECKCFL (HipContext.propags).  1 (PROPAGS1) is not served.
-        if ipropags not in (0, 2):
-            raise ValueError("ipropags must be 0 (PROPAGS) or 2 (PROPAGS2); IPROPAGS = 1 is not served")
-        if ipropags == 0 and ifrelfmax > 0:
-            raise ValueError("ipropags = 0 has no fast-wave sub-steps: PROPAG_WAM sub-steps only in CASE(2) (ifrelfmax must be 0)")
-        if ipropags == 0 and weights == "stored":
-            raise ValueError("ipropags = 0 has no stored weights: PROPAGS forms its weights in every call (weights must be 'otf')")
+        # 0 = PROPAGS, the first-order upwind scheme with CHECKCFL (HipContext.propags); 1 = PROPAGS1, the first-order scheme on two rotated
+        # quadrants (HipContext.propags1), which reads the tables of grid.rotated_tables (rotated=...), whole grid only.
+        if ipropags not in (0, 1, 2):
+            raise ValueError("ipropags must be 0, 1 or 2")
+        if ipropags == 1 and rotated is None:
+            raise ValueError("IPROPAGS = 1 needs the rotated tables of grid.rotated_tables (rotated=...)")
+        if ipropags != 2 and ifrelfmax > 0:
+            raise ValueError(f"ipropags = {ipropags} has no fast-wave sub-steps: PROPAG_WAM sub-steps only in CASE(2) (ifrelfmax must be 0)")
+        if ipropags != 2 and weights == "stored":
+            raise ValueError(f"ipropags = {ipropags} has no stored weights: the first-order schemes form their weights in every call (weights must be 'otf')")
+        if ipropags == 1 and nranks > 1:
+            raise ValueError("ipropags = 1 runs on one rank: the halo of the decomposition does not hold the rotated neighbours (nranks must be 1)")
         self.ipropags = ipropags
         # weights: "otf" rebuilds the CTU weights inside PROPAGS2 (no W array, default); "stored" keeps the reference's
         # scheme (CTUW once into W[ij][8][NANG*NFRE_RED], PROPAGS2 streams them).  Bit-identical results.
@@ -156,7 +161,7 @@ class Wamintgr:
         elif strip_width < 0:      # 2-D tiles of four latitude rows x four longitudes
             self.order = torch.from_numpy(decomp.tile2d_order(grid, self.dom)).to(self.dev)
             self.tiles2d = True
-        if self.order is not None and (int(cfg.irefra) or weights == "stored" or ipropags == 0):
+        if self.order is not None and (int(cfg.irefra) or weights == "stored" or ipropags != 2):
             # the refraction and stored-weight kernels walk the rows in their natural order: a work order (whose padded length would
             # otherwise replace the row range handed to them) does not apply
             self.order, self.tiles2d = None, False
@@ -198,7 +203,7 @@ class Wamintgr:
             self.v_ext = torch.zeros(self.nrows, **z)
             self.omosnh2kd_ext = torch.zeros((self.nrows, NFRE), **z)
             self.wavnum_ext = torch.zeros((self.nrows, NFRE), **z)
-        if ipropags == 0:
+        if ipropags != 2:
             # DELLAM1_EXT = 1 / DELLAM(KXLT) of the owned and the halo rows, DELLAM = ZDELLO CIRC / 360 (readmdlconf.F90:145, mpdecomp.F90:1428); land slot 0
             T = self.npdt
             dellam = np.asarray(grid.zdello, T) * T(self.t.CIRC) / T(360.0)
@@ -206,6 +211,8 @@ class Wamintgr:
             d1[:self.dom.nland] = T(1) / dellam[np.asarray(grid.kxlt)[self.dom.ext_global()]]
             self.gd = dict(self.gd, dellam1_ext=torch.from_numpy(d1).to(self.dev))
             self.dot = torch.zeros((self.n, 3 * NANG + 4), **z) if self.irefra else None
+        if ipropags == 1:
+            self.ctx.set_rotated(api.rotated_to_device(rotated, self.dtype, self.dev))
 
     @property
     def fast_mode(self) -> str:
@@ -324,11 +331,12 @@ class Wamintgr:
     def build_weights(self) -> int:
         c = self.cfg
         self.cflfail.zero_()
-        if self.ipropags == 0:
-            # PROPDOT with refraction (propag_wam.F90:343-350), then CHECKCFL as PROPAGS calls it, without a spectrum written
+        if self.ipropags != 2:
+            # PROPDOT with refraction (propag_wam.F90:298-305, 343-350), then CHECKCFL as PROPAGS / PROPAGS1 calls it, without a spectrum written
             if self.irefra:
                 self.ctx.propags_dot(self.gd, self.depth_ext, self.u_ext, self.v_ext, self.dot)
-            self.ctx.propags(self.fl1, None, self.gd, self.cgroup_ext, float(c.idelpro), 0, self.n, cflfail=self.cflfail, **self._propags_env())
+            first_order = self.ctx.propags1 if self.ipropags == 1 else self.ctx.propags
+            first_order(self.fl1, None, self.gd, self.cgroup_ext, float(c.idelpro), 0, self.n, cflfail=self.cflfail, **self._propags_env())
             self.weights_ready = True
             return int(self.cflfail.sum().item())
         if self.irefra:
@@ -370,12 +378,12 @@ class Wamintgr:
         e1.record()
         self.halo_events.append((e0, e1))
 
-    # ---- PROPAG_WAM (propag_wam.F90:166-313), IPROPAGS = 2; (propag_wam.F90:341-362), IPROPAGS = 0
+    # ---- PROPAG_WAM (propag_wam.F90:166-313), IPROPAGS = 2; (propag_wam.F90:341-362), IPROPAGS = 0; (propag_wam.F90:296-322), IPROPAGS = 1
     def propag(self) -> None:
         if not self.weights_ready:
             nfail = self.build_weights()
             if nfail:
-                where = "checkcfl.F90:74-247" if self.ipropags == 0 else "ctuwdrv.F90:128-146"
+                where = "checkcfl.F90:74-247" if self.ipropags != 2 else "ctuwdrv.F90:128-146"
                 raise api.EcwamHipError(f"CFL criterion violated at {nfail} points ({where})")
         c, g = self.cfg, self.gd
         lf = 0 < self.ifrelfmax < c.nfre_red
@@ -383,8 +391,9 @@ class Wamintgr:
         def advect_rows(k0, k1, m1, m2, delpro, copy_rest, split=0, src=None):
             if k1 <= k0:
                 return
-            if self.ipropags == 0:
-                self.ctx.propags(self.fl1, self.fl3, g, self.cgroup_ext, delpro, k0, k1, copy_rest=copy_rest, **self._propags_env())
+            if self.ipropags != 2:
+                first_order = self.ctx.propags1 if self.ipropags == 1 else self.ctx.propags
+                first_order(self.fl1, self.fl3, g, self.cgroup_ext, delpro, k0, k1, copy_rest=copy_rest, **self._propags_env())
                 return
             tiled = self.tiles2d and (k0, k1) == (0, self.n)
             if tiled:                                        # the range indexes the entries of the (padded) tile order

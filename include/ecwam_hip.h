@@ -132,6 +132,8 @@ int ecwam_hip_destroy(ecwam_hip_ctx *ctx);
  * the space weights with them).  obs: device real OBS[n][8][NFRE], planes OBSLAT(IJ,M,1:2), OBSLON(IJ,M,1:2), OBSCOR(IJ,M,1:4)
  * (values in [0,1], 1 = open); the library keeps the POINTER (the caller owns the memory) and every later ecwam_hip_ctuw /
  * ecwam_hip_propags2_otf / ecwam_hip_propags2_refra applies it.  obs = NULL switches it off (LSUBGRID = F, the default).
+ * With IPROPAGS = 1 (ecwam_hipx_propags1.h) the last four planes are read as OBSRLAT(IJ,M,1:2) (planes 4-5) and OBSRLON(IJ,M,1:2) (planes 6-7), the
+ * order of the file getbobstrct.F90 reads: that scheme has no corner points and the corner-transport scheme no rotated ones.
  */
 int ecwam_hip_set_obstructions(ecwam_hip_ctx *ctx, const void *obs, int n);
 

@@ -13,7 +13,8 @@
  * divisions.  PROPAGS, CHECKCFL, PROPDOT and GRADI hold only + - * / and ABS (MIN and SIGN in the clamp of the current gradients), so the results are
  * the bits of the reference compiled without contraction.
  *
- * Not served: IPROPAGS = 1 (PROPAGS1), fast-wave sub-steps (PROPAG_WAM sub-steps only in CASE(2)), the one-kernel step.
+ * Not served: fast-wave sub-steps (PROPAG_WAM sub-steps only in CASE(2)), the one-kernel step.  IPROPAGS = 1 (PROPAGS1) has a header of its own,
+ * ecwam_hipx_propags1.h.
  */
 #ifndef ECWAM_HIP_PROPAGS_H
 #define ECWAM_HIP_PROPAGS_H
